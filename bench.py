@@ -1,6 +1,6 @@
 """Headline benchmark: i2c EM iterations/s and timestep-messages/s, pendulum T=200, B=4096 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--horizon T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--horizon T] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 starts its own N workers (one process per GPU through torch.distributed.run on 127.0.0.1) unless it
 is already running under torchrun (RANK / WORLD_SIZE in the environment, the way the driver launches it).
@@ -10,10 +10,14 @@ M-step) over the whole local batch; inputs are resident in HBM before the timed 
 cell-iteration ("timestep-message") = one (trajectory, timestep) cell through forward message +
 backward message + M-step statistics. N > 1: one process per GPU (torchrun),
 the batch axis is sharded with no collective inside the EM loop (weak scaling: B per GPU is
-fixed); the single RCCL all-gather of the final controllers runs after the timed steps and is
-reported separately. Two STRONG-scaling legs (global batch 4096 and 65536 split over the ranks) and, at
-N = 1, legs for the other BASELINE configs (double cartpole T=300 B=4096, 12-state quadrotor MPC step H=50 B=8192,
-pendulum covariance control T=100 B=8192) ride on the same JSON line.
+fixed).
+
+A plain run does only what the headline figure needs: set up, W warm-up iterations, the K timed iterations (ONE i2c_learn
+call), the outputs of the last one if `--dump-outputs DIR` is given, the JSON line. Everything else is measured with `--full`:
+per-kernel event timing, the 200-iteration long run, the single RCCL all-gather of the final controllers (a single-rank
+RCCL group at N = 1), the roofline, two STRONG-scaling legs (global batch 4096 and 65536 split over the ranks)
+and, at N = 1, the saturated-batch legs, legs for the other BASELINE configs (double cartpole T=300 B=4096, 12-state
+quadrotor MPC step H=50 B=8192, pendulum covariance control T=100 B=8192) and the CPU baseline, all on the same JSON line.
 
 Prints ONE JSON line on rank 0.
 """
@@ -112,6 +116,38 @@ def saturated_leg(pkg, T, dtype, device, el, wbytes, B=131072, K=6, storage_dtyp
         "whole_iteration_GBps": el["total"] * wbytes * cells / (elapsed / K) / 1e9,
         "whole_iteration_frac_of_peak": el["total"] * wbytes * cells / (elapsed / K) / 1e9 / HBM_PEAK_GBS,
     }
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(eng, out_dir, suffix="", budget=DUMP_BUDGET_BYTES):
+    """What the timed i2c_learn call hands its caller after its last EM iteration, as float64 `<out_dir>/<name><suffix>.npy`:
+    the posterior marginals of (x, u) per cell (mu_xu (B, T, d), sig_xu (B, T, d, d)), the local linear policy (K, k, sigK) and,
+    per trajectory, the temperature, the last M-step's alpha_hat, expected cost and its variance, and the status word. A batch
+    whose arrays exceed `budget` bytes is written for a fixed sample of its trajectories (default_rng(0), trajectory 0 always
+    in); `trajectory_index` lists the ones written. Returns (file names, trajectories written, bytes)."""
+    B = eng.B
+    mu, sig = eng.marginal_state_action()
+    K, k, sigK = eng.local_linear_policy()
+    arrays = dict(mu_xu=mu, sig_xu=sig, K=K, k=k, sigK=sigK, alpha=eng.alpha, status=eng.status)
+    for name, hist in (("alpha_hat", eng.alphas_desired), ("cost", eng.costs_m), ("cost_var", eng.costs_m_var)):
+        if hist:
+            arrays[name] = hist[-1]
+    per_trajectory = 8 * (1 + sum(int(np.prod(a.shape[1:])) for a in arrays.values()))  # (+ its entry of trajectory_index)
+    n = max(1, min(B, budget // per_trajectory))
+    idx = np.arange(B)
+    if n < B:
+        idx = np.concatenate(([0], np.sort(np.random.default_rng(0).choice(np.arange(1, B), n - 1, replace=False))))
+    sel = torch.as_tensor(idx, device=eng.device)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays["trajectory_index"] = torch.as_tensor(idx, dtype=torch.float64)
+    total = 0
+    for name, a in arrays.items():
+        a = (a if name == "trajectory_index" else a.index_select(0, sel)).to(torch.float64).cpu().numpy()
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a))
+        total += a.nbytes
+    return sorted(name + suffix + ".npy" for name in arrays), n, total
 
 
 def algorithmic_elements(d, nx, nu):
@@ -565,6 +601,13 @@ def main():
     ap.add_argument("--batch", type=int, default=4096, help="trajectories PER GPU")
     ap.add_argument("--horizon", type=int, default=200)
     ap.add_argument("--dtype", default="f64", choices=["f64"], help="the path computes in fp64 (the reference's arithmetic)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as float64 DIR/<name>.npy (at most 64 MB in all: a "
+                         "fixed sample of the trajectories beyond that; with N > 1 every rank writes <name>_rank<r>.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: per-kernel timing, the long run, the final all-gather, "
+                         "roofline, strong scaling, the saturated batch, the other BASELINE configs, the CPU baseline (the --no-* "
+                         "switches below leave parts of it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-saturated", action="store_true", help="skip the extra B=131072 leg")
     ap.add_argument("--no-extra", action="store_true", help="skip the legs of the other BASELINE configs and strong scaling")
@@ -603,8 +646,8 @@ def main():
             dist.init_process_group("gloo")
         else:
             dist.init_process_group("nccl", device_id=device)  # RCCL on ROCm
-    elif args.gpus == 1 and not args.test_hostsim and not args.no_rccl:
-        # A plain `python bench.py` (how the driver runs N = 1): a single-rank RCCL group in this process, so that the job's one
+    elif args.full and args.gpus == 1 and not args.test_hostsim and not args.no_rccl:
+        # `python bench.py --full` at N = 1: a single-rank RCCL group in this process, so that the job's one
         # collective -- the all-gather of the final controllers -- runs through the same code path as N > 1 and the line
         # carries its time. Nothing is re-executed; the group is created before any kernel of the benchmark runs.
         import socket
@@ -641,15 +684,9 @@ def main():
     for _ in range(args.warmup):
         eng.learn_msgs()
 
-    # ---- per-kernel timing: K EM iterations stepped from Python with HIP events around each sweep -----
-    K = args.steps
-    if device.type == "cuda":
-        stepwise_s, (fwd_ms, bwd_ms, mst_ms) = timed_iterations(eng, K, barrier)
-    else:
-        stepwise_s, (fwd_ms, bwd_ms, mst_ms) = 0.0, (float("nan"),) * 3
-
     # ---- THE timed region: exactly K EM iterations, enqueued by ONE i2c_learn call (the way a caller runs
     # N iterations: no Python between sweeps), bracketed by barrier + synchronize on both sides ---------
+    K = args.steps
     barrier()
     t0 = time.perf_counter()
     eng.learn(K)
@@ -659,6 +696,53 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    n_fail = len(eng.failures())
+    dumped = None
+    if args.dump_outputs:  # (before anything else runs on the engine: the state of the last timed step)
+        files, n_dumped, nbytes = dump_outputs(eng, args.dump_outputs, f"_rank{rank}" if world > 1 else "",
+                                               DUMP_BUDGET_BYTES // world)
+        dumped = {"dir": args.dump_outputs, "files": files, "trajectories": n_dumped, "of": B, "bytes": nbytes}
+
+    out = {
+        "metric": "i2c timestep-messages/sec (cell-iterations/s = B*T*EM-iters/s), pendulum T=200 B=4096 per GPU",
+        "value": B * T * world * K / elapsed,
+        "unit": "timestep-messages/s",
+        "em_iters_per_sec": K / elapsed,
+        "n_gpus": world,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / K * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic" if not args.test_hostsim else "synthetic (TEST MODE: host simulation on CPU, numbers meaningless)",
+        "config": {
+            "workload": f"pendulum_known_quad cubature i2c (nx=2, nu=1, nz=4), T={T}, B={B} trajectories per GPU, "
+                        f"global batch {B * world}, CubatureQuadrature(1,0,0), alpha0=100, tol=0",
+            "batch_per_gpu": B,
+            "horizon": T,
+            "parallelism": f"batch-sharded x{world}, no collective in the EM loop",
+            "kernels": "group, %d lanes per trajectory" % args.group_lanes if args.group_lanes else "one lane per trajectory",
+        },
+        "backward": eng.backward_schedule,
+        "failed_trajectories": n_fail,
+        "full": args.full,
+    }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if not args.full:
+        if dist is not None:
+            dist.destroy_process_group()
+        if rank == 0:
+            emit(out)
+        return
+
+    # ---- --full: per-kernel timing, K EM iterations stepped from Python with HIP events around each sweep -----
+    if device.type == "cuda":
+        stepwise_s, (fwd_ms, bwd_ms, mst_ms) = timed_iterations(eng, K, barrier)
+    else:
+        stepwise_s, (fwd_ms, bwd_ms, mst_ms) = 0.0, (float("nan"),) * 3
     # ---- the same loop over max(K, 200) iterations (round-4 review, weak #12: the contract's K = 20 steps are a 7 ms region, in which
     # one stray 50 us hiccup is 0.7 %): reported NEXT TO the K-step figure, which stays the line's `value` -----------------------------
     n_long = max(K, 200)
@@ -671,7 +755,6 @@ def main():
         tmax = torch.tensor([elapsed_long], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed_long = float(tmax.item())
-    n_fail = len(eng.failures())
 
     # ---- the one collective of the job: all-gather of the final controllers -------
     allgather_ms = None
@@ -712,37 +795,15 @@ def main():
     el = algorithmic_elements(eng.d, eng.nx, eng.nu)
     fwd_bytes = el["forward"] * wbytes * B * T  # per launch of the forward-sweep kernel
     achieved = fwd_bytes / (fwd_ms * 1e-3) / 1e9
-    out = {
-        "metric": "i2c timestep-messages/sec (cell-iterations/s = B*T*EM-iters/s), pendulum T=200 B=4096 per GPU",
-        "value": cells * K / elapsed,
-        "unit": "timestep-messages/s",
-        "em_iters_per_sec": K / elapsed,
-        "n_gpus": world,
-        "steps": K,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / K * 1e3,
+    out.update({
         "long_run": {"steps": n_long, "ms_per_step": elapsed_long / n_long * 1e3, "value": cells * n_long / elapsed_long,
                      "note": "the same timed loop over max(steps, 200) EM iterations: the noise floor of the K-step figure"},
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": args.dtype,
-        "data": "synthetic" if not args.test_hostsim else "synthetic (TEST MODE: host simulation on CPU, numbers meaningless)",
-        "config": {
-            "workload": f"pendulum_known_quad cubature i2c (nx=2, nu=1, nz=4), T={T}, B={B} trajectories per GPU, "
-                        f"global batch {B * world}, CubatureQuadrature(1,0,0), alpha0=100, tol=0",
-            "batch_per_gpu": B,
-            "horizon": T,
-            "parallelism": f"batch-sharded x{world}, no collective in the EM loop",
-            "kernels": "group, %d lanes per trajectory" % args.group_lanes if args.group_lanes else "one lane per trajectory",
-        },
         "rccl_world_size": (dist.get_world_size() if dist is not None else None),
         "rccl_backend": (dist.get_backend() if dist is not None else None),
         "rccl_error": rccl_error,
         "kernel_ms": {"forward_sweep": fwd_ms, "backward_sweep": bwd_ms, "mstep": mst_ms},
-        "backward": eng.backward_schedule,
         "ms_per_step_stepped_from_python": stepwise_s / K * 1e3,
-        "failed_trajectories": n_fail,
+        "failed_trajectories": len(eng.failures()),  # (after every iteration of the engine: timed, stepped and long run)
         "roofline": {
             "kernel": "k_forward (forward sweep, the dominant kernel)",
             "bound": "hbm",
@@ -767,7 +828,7 @@ def main():
         "strong_scaling": strong,
         # what every rank ran (the default family and the backward schedule depend on the shard size: DESIGN.md section 8)
         "families_per_rank": families,
-    }
+    })
     if device.type == "cuda":
         if not args.no_saturated and world == 1:
             out["saturated_batch"] = saturated_leg(pkg, T, dtype, device, el, wbytes)
@@ -783,10 +844,14 @@ def main():
             out["extra"]["reference_shapes"] = reference_shape_legs(pkg, device)
         if not args.no_cpu_baseline and world == 1:  # the CPU baseline is reported at N = 1 only
             out["cpu_baseline"] = cpu_baseline(T)
-    # the JSON line is the LAST thing on stdout: tear the process group down first and flush the C runtime's buffer (RCCL prints a
-    # version banner through it, which otherwise lands after Python's output when stdout is a pipe)
     if dist is not None:
         dist.destroy_process_group()
+    emit(out)
+
+
+def emit(out):
+    """The JSON line is the LAST thing on stdout: the caller tears the process group down first; the C runtime's buffer is
+    flushed here (RCCL prints a version banner through it, which otherwise lands after Python's output when stdout is a pipe)."""
     try:
         import ctypes
 

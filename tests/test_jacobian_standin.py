@@ -5,9 +5,10 @@ autograd is not installed in the build container) pinned by something OTHER than
 * double cartpole (reference i2c/env_autograd.py:60-167): an independent scheme -- central differences at two step sizes with
   Richardson extrapolation (error O(h^4)) -- which shares no code with the complex-step stand-in.
 
-Both to <= 1e-9 of the Jacobian's largest entry. The functions differentiated are the REFERENCE's own when /root/reference is
-present (imported in a child process through the shim: this process has the build's package under the name `i2c`), and always the
-oracle's NumPy twins (oracle/models_numpy.py, pinned to the reference by tests/golden/models_vectors.npz)."""
+Both to <= 1e-9 of the Jacobian's largest entry. The functions differentiated are the REFERENCE's own -- replayed from their
+recorded calls (tests/golden/reference_dynamics_calls.npz, oracle/gen_reference_dynamics_golden.py) and, where the reference checkout
+is present, live as well (imported in a child process through the shim: this process has the build's package under the name
+`i2c`) -- and the oracle's NumPy twins (oracle/models_numpy.py, pinned to the reference by tests/golden/models_vectors.npz)."""
 import json
 import os
 import subprocess
@@ -97,8 +98,34 @@ print(json.dumps({{"dcp_err": err}}))
 """
 
 
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="/root/reference is not present on this machine")
+class Replay:
+    """One of the reference's dynamics functions replayed from its recorded calls (input -> output, matched exactly on the input,
+    complex-step inputs included). A miss raises -- and is counted, since the stand-in treats any exception of a complex call as
+    "not complex-safe"."""
+
+    def __init__(self, z, tag):
+        self.calls = [(z[f"{tag}_x{i}"], z[f"{tag}_y{i}"]) for i in range(int(z[tag + "_n"]))]
+        self.misses = 0
+
+    def __call__(self, x):
+        x = np.asarray(x)
+        for xi, yi in self.calls:
+            if xi.dtype == x.dtype and xi.shape == x.shape and np.array_equal(xi, x):
+                return yi.copy()
+        self.misses += 1
+        raise KeyError("no recorded call of the reference with this input")
+
+
 def test_standin_on_the_reference_dynamics():
+    z = np.load(os.path.join(ROOT, "tests", "golden", "reference_dynamics_calls.npz"))
+    pend, dcp = Replay(z, "pendulum"), Replay(z, "double_cartpole")
+    assert check(pend, dcp, "reference (recorded)") <= 1e-9
+    assert pend.misses == 0 and dcp.misses == 0, "the stand-in asked the recorded reference for a call it never made"
+    # what the reference itself calls at run time: the module-level Jacobians built from the stand-in at import
+    jp = z["pendulum_dydxu"]
+    assert np.max(np.abs(np.stack([jp[p, :, p, :] for p in range(4)]) - pendulum_jacobian_closed_form(PEND_XU))) <= 1e-12 * 2
+    if not ref_shim.reference_available():
+        return
     code = _CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))

@@ -9,11 +9,11 @@ TAG=${1:-profiles_run}
 OUT="$PWD/gpurun_out/$TAG"
 mkdir -p "$OUT"
 F="--output-format csv"
-SMALL="--steps 50 --warmup 5 --no-cpu-baseline --no-saturated"
+SMALL="--full --steps 50 --warmup 5 --no-cpu-baseline --no-saturated"
 rocprofv3 --kernel-trace --stats $F -d "$OUT/kt" -- python3 bench.py $SMALL > "$OUT/bench_kt.json" 2> "$OUT/log_kt.txt"
-rocprofv3 --pmc FETCH_SIZE $F -d "$OUT/f4096" -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-saturated > /dev/null 2> "$OUT/log_f.txt"
-rocprofv3 --pmc WRITE_SIZE $F -d "$OUT/w4096" -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-saturated > /dev/null 2> "$OUT/log_w.txt"
-BIG="--batch 131072 --no-cpu-baseline --no-saturated"
+rocprofv3 --pmc FETCH_SIZE $F -d "$OUT/f4096" -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-saturated > /dev/null 2> "$OUT/log_f.txt"
+rocprofv3 --pmc WRITE_SIZE $F -d "$OUT/w4096" -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-saturated > /dev/null 2> "$OUT/log_w.txt"
+BIG="--full --batch 131072 --no-cpu-baseline --no-saturated"
 rocprofv3 --kernel-trace --stats $F -d "$OUT/ktbig" -- python3 bench.py $BIG --steps 20 --warmup 2 > "$OUT/bench_ktbig.json" 2> "$OUT/log_ktbig.txt"
 rocprofv3 --pmc FETCH_SIZE $F -d "$OUT/fbig" -- python3 bench.py $BIG --steps 10 --warmup 2 > /dev/null 2> "$OUT/log_fb.txt"
 rocprofv3 --pmc WRITE_SIZE $F -d "$OUT/wbig" -- python3 bench.py $BIG --steps 10 --warmup 2 > /dev/null 2> "$OUT/log_wb.txt"
@@ -21,5 +21,5 @@ python3 tools/pmc_summary.py "tmp_${TAG}_B4096" 4096 200 "$OUT/f4096" "$OUT/w409
 python3 tools/pmc_summary.py "tmp_${TAG}_B131072" 131072 200 "$OUT/fbig" "$OUT/wbig" > /dev/null
 cp profiles/tmp_${TAG}_*_pmc_traffic.json "$OUT/"
 find "$OUT" -name "*.csv" -size +3M -delete
-python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/log_default.txt"
+python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/log_default.txt"
 du -sh "$OUT"

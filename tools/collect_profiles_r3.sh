@@ -10,10 +10,10 @@ export TMPDIR=/tmp
 OUT="$PWD/gpurun_out/r3"
 rm -rf "$OUT"; mkdir -p "$OUT"
 F="--output-format csv"
-SMALL="--steps 50 --warmup 5 --no-cpu-baseline --no-saturated --no-extra"
+SMALL="--full --steps 50 --warmup 5 --no-cpu-baseline --no-saturated --no-extra"
 rocprofv3 --kernel-trace --stats $F -d "$OUT/kt" -- python3 bench.py $SMALL > "$OUT/bench_kt.json" 2> "$OUT/log_kt.txt"
-rocprofv3 --pmc FETCH_SIZE $F -d "$OUT/f4096" -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-saturated --no-extra > /dev/null 2> "$OUT/log_f.txt"
-rocprofv3 --pmc WRITE_SIZE $F -d "$OUT/w4096" -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-saturated --no-extra > /dev/null 2> "$OUT/log_w.txt"
+rocprofv3 --pmc FETCH_SIZE $F -d "$OUT/f4096" -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-saturated --no-extra > /dev/null 2> "$OUT/log_f.txt"
+rocprofv3 --pmc WRITE_SIZE $F -d "$OUT/w4096" -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-saturated --no-extra > /dev/null 2> "$OUT/log_w.txt"
 python3 tools/pmc_summary.py "r3_B4096" 4096 200 "$OUT/f4096" "$OUT/w4096" > "$OUT/pmc_B4096.txt"
 # 12-state quadrotor: kernel stats of both families at the per-GPU share of config 4 (B = 1024) and at B = 4096
 for B in 1024 4096; do

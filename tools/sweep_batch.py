@@ -4,7 +4,7 @@ import subprocess
 import sys
 
 for B in [int(a) for a in sys.argv[1:]] or [512, 1024, 2048, 4096, 8192, 16384, 32768, 65536, 131072]:
-    out = subprocess.run([sys.executable, "bench.py", "--batch", str(B), "--steps", "30", "--warmup", "3", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--batch", str(B), "--steps", "30", "--warmup", "3", "--no-cpu-baseline",
                           "--no-saturated", "--no-extra"], capture_output=True, text=True).stdout.strip().split("\n")
     out = [l for l in out if l.startswith("{")][-1]
     d = json.loads(out)
