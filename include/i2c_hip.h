@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define I2C_ABI_VERSION 7
+#define I2C_ABI_VERSION 8
 
 #define I2C_MAX_NX 12
 #define I2C_MAX_NU 4
@@ -245,6 +245,11 @@ typedef struct I2cProblem {
   const uint8_t* expert;      /* optional [T] bytes (ring): per-cell use_expert_controller (i2c.py:143), read by the
                                  closed-loop propagation (i2c.py:160) and the Linearize forward pass (i2c.py:259); NULL: every
                                  cell takes the scalar flag (expert_controller / the argument of i2c_propagate)  */
+  const void* model_params_b; /* optional [NP][B], arithmetic dtype (double in I2C_F64_F32S): per-trajectory model parameters.
+                                 NULL: model_params serves every trajectory. Otherwise trajectory b's dynamics / observe / measure
+                                 read column b (parameter i at i * B + b) in every sweep, filter step and rollout (rollout n:
+                                 column n % B). I2C_EINVAL on a model with n_params = 0. Kernel families and backward schedules
+                                 are the same as without it (i2c_kernel_family, i2c_backward_schedule).                    */
 } I2cProblem;
 
 /*

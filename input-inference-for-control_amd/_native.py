@@ -9,7 +9,7 @@ without a GPU; nothing in the package ever looks for it.)
 import ctypes as C
 import os
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_NX, MAX_NU, MAX_NZ, MAX_PARAMS = 12, 4, 16, 16
 MAX_GH_DEGREE = 8
 
@@ -101,6 +101,7 @@ class I2cProblem(C.Structure):
         ("work", C.c_void_p),
         ("feedforward", C.c_void_p),
         ("expert", C.c_void_p),
+        ("model_params_b", C.c_void_p),  # optional [NP][B] per-trajectory model parameters (arithmetic dtype)
     ]
 
 

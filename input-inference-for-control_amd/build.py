@@ -36,12 +36,20 @@ def sources():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [INCLUDE]
 
 
+def model_tus(struct, name, extra=()):
+    """The translation units of one model: per precision the shared-parameter table and, in a unit of its own, the
+    per-trajectory-parameter one (-DI2C_TU_PER_TRAJ; empty for a model without parameters). [(object name, source, -D flags)]"""
+    tus = []
+    for real, tag, store in DTYPES:
+        defs = list(extra) + [f"-DI2C_TU_MODEL={struct}", f"-DI2C_TU_REAL={real}", f"-DI2C_TU_OPS=ops_{name}_{tag}",
+                              f"-DI2C_TU_OPS_PT=ops_{name}_{tag}_pt"] + ([f"-DI2C_TU_STORE={store}"] if store else [])
+        tus += [(f"{name}_{tag}.o", "i2c_model_tu.hip", defs), (f"{name}_{tag}_pt.o", "i2c_model_tu.hip", defs + ["-DI2C_TU_PER_TRAJ"])]
+    return tus
+
+
 def translation_units():
     """[(object name, source, extra -D flags)]"""
-    tus = [(f"{name}_{tag}.o", "i2c_model_tu.hip",
-            [f"-DI2C_TU_MODEL={struct}", f"-DI2C_TU_REAL={real}", f"-DI2C_TU_OPS=ops_{name}_{tag}"]
-            + ([f"-DI2C_TU_STORE={store}"] if store else []))
-           for struct, name in MODELS for real, tag, store in DTYPES]
+    tus = [tu for struct, name in MODELS for tu in model_tus(struct, name)]
     return tus + [("capi.o", "i2c_capi.hip", [])]
 
 
@@ -100,10 +108,7 @@ def build_model(header, struct=None, name=None, host_sim=False, out_dir=None, fo
     obj_dir = os.path.join(OBJ_DIR, f"model_{name}{'_hostsim' if host_sim else ''}")
     os.makedirs(obj_dir, exist_ok=True)
     os.makedirs(os.path.dirname(lib), exist_ok=True)
-    tus = [(f"{name}_{tag}.o", "i2c_model_tu.hip",
-            [f'-DI2C_TU_HEADER="{header}"', f"-DI2C_TU_MODEL={struct}", f"-DI2C_TU_REAL={real}", f"-DI2C_TU_OPS=ops_{name}_{tag}"]
-            + ([f"-DI2C_TU_STORE={store}"] if store else []))
-           for real, tag, store in DTYPES] + [("entry.o", "i2c_model_entry.hip", [f"-DI2C_PLUGIN_NAME={name}"])]
+    tus = model_tus(struct, name, [f'-DI2C_TU_HEADER="{header}"']) + [("entry.o", "i2c_model_entry.hip", [f"-DI2C_PLUGIN_NAME={name}"])]
 
     def one(tu):
         obj, src, defs = tu

@@ -61,6 +61,13 @@ int check_problem_shape(const I2cProblem* p) {
     ops->dims(&d);
     if (!d.wave) return I2C_ENOTSUP;
   }
+  if (p->model_params_b) {  // per-trajectory parameters: nothing to vary on a model without parameters
+    I2cDims d;
+    const i2c::ModelOps* ops = find_ops(p->model_id, I2C_F64);
+    if (!ops) return I2C_EINVAL;
+    ops->dims(&d);
+    if (d.n_params == 0) return I2C_EINVAL;
+  }
   return I2C_OK;
 }
 
@@ -72,6 +79,7 @@ int check_problem_shape(const I2cProblem* p) {
     const int rc_ = check_problem(p);                                     \
     if (rc_ != I2C_OK) return rc_;                                        \
     const i2c::ModelOps* ops_ = find_ops((p)->model_id, (p)->dtype);      \
+    if (ops_ && (p)->model_params_b) ops_ = ops_->per_traj;               \
     if (!ops_) return I2C_EINVAL;                                         \
     return ops_->CALL;                                                    \
   } while (0)

@@ -12,6 +12,7 @@
 //   * the controller (K, k, sigK) falls out of the Cholesky factor of the posterior joint.
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/i2c_hip.h"
 #include "i2c_linalg.hpp"
 #include "i2c_models.hpp"
@@ -31,7 +32,20 @@ template <typename R> struct Rule {
   R gh_x[I2C_MAX_GH_DEGREE], gh_w[I2C_MAX_GH_DEGREE];
 };
 
-template <class M, typename R> struct Consts {
+// Per-trajectory model parameters (I2cProblem.model_params_b) are a compile-time flag carried by the model type: every kernel
+// instantiated on PerTraj<M> evaluates trajectory b's functors with column b of the [NP][B] device array c.params_b; the
+// kernels of M itself keep reading the batch constants c.params from the kernel-argument segment. Only models with NP > 0
+// get the PerTraj instantiations (make_ops, i2c_impl.hpp).
+template <class M> struct PerTraj : M {};
+template <class M> struct is_per_traj : std::false_type {};
+template <class M> struct is_per_traj<PerTraj<M>> : std::true_type {};
+// ... and the [NP][B] array itself, a member of Consts<PerTraj<M>, R> only (an empty base otherwise: the kernel arguments of the
+// shared-parameter kernels are laid out as without the feature)
+template <typename R, bool PER_TRAJ> struct ParamsB {};
+template <typename R> struct ParamsB<R, true> {
+  const R* params_b;
+};
+template <class M, typename R> struct Consts : ParamsB<R, is_per_traj<M>::value> {
   static constexpr int NX = M::NX, NU = M::NU, NZ = M::NZ, NZT = M::NZT, D = NX + NU;
   static constexpr int NZT1 = NZT > 0 ? NZT : 1, NP1 = M::NP > 0 ? M::NP : 1;
   static constexpr int E_PRI = D + sym(D) + NU * NX;                        // rows the forward reads
@@ -64,22 +78,63 @@ template <class M, typename R> struct Consts {
   R zg[NZ], zg_term[NZT1], mu_x_term[NX], sig_x_term[sym(NX)], params[NP1];
 };
 
-// The three model callbacks as functors: f(x, sin(angles of x), cos(angles of x), y).
-template <class M, typename R> struct ObserveF {
+// column b of the [NP][B] array: parameter i at p[i * B]
+template <typename R> struct ParamCol {
   const R* p;
-  I2C_HD inline void operator()(const R* x, const R* sn, const R* cs, R* y) const { M::observe(p, x, sn, cs, y); }
+  long B;
+};
+template <class M, typename R> using ParamSrc = std::conditional_t<is_per_traj<M>::value, ParamCol<R>, const R*>;
+// where trajectory b's functors read their parameters (b in [0, B): the multi-lane kernels pass a clamped index for dead lanes)
+template <class M, typename R> I2C_FN ParamSrc<M, R> params_of(const Consts<M, R>& c, const int b) {
+  if constexpr (is_per_traj<M>::value) return ParamCol<R>{c.params_b + b, (long)c.B};
+  else return c.params;
+}
+// ... gathered into the functor's `const R* p` at the point of use (L1 / L2 resident, so nothing has to stay live in registers
+// across a sweep: the kernels that evaluate the functors are the register-heavy ones); the shared-parameter kernels pass c.params
+// itself, in code that is the same as without the feature
+template <int NP, typename R> I2C_FN const R* param_ptr(const ParamCol<R>& s, R* buf) {
+#pragma unroll
+  for (int i = 0; i < NP; ++i) buf[i] = s.p[i * s.B];
+  return buf;
+}
+
+// The three model callbacks as functors: f(x, sin(angles of x), cos(angles of x), y), parameters from params_of().
+template <class M, typename R> struct ObserveF {
+  ParamSrc<M, R> p;
+  I2C_HD inline void operator()(const R* x, const R* sn, const R* cs, R* y) const {
+    if constexpr (is_per_traj<M>::value) {
+      R pb[M::NP];
+      M::observe(param_ptr<M::NP>(p, pb), x, sn, cs, y);
+    } else {
+      M::observe(p, x, sn, cs, y);
+    }
+  }
 };
 template <class M, typename R> struct DynamicsF {
-  const R* p;
-  I2C_HD inline void operator()(const R* x, const R* sn, const R* cs, R* y) const { M::dynamics(p, x, sn, cs, y); }
+  ParamSrc<M, R> p;
+  I2C_HD inline void operator()(const R* x, const R* sn, const R* cs, R* y) const {
+    if constexpr (is_per_traj<M>::value) {
+      R pb[M::NP];
+      M::dynamics(param_ptr<M::NP>(p, pb), x, sn, cs, y);
+    } else {
+      M::dynamics(p, x, sn, cs, y);
+    }
+  }
 };
 template <class M, typename R> struct MeasureF {
-  const R* p;
-  I2C_HD inline void operator()(const R* x, const R* sn, const R* cs, R* y) const { M::measure(p, x, sn, cs, y); }
+  ParamSrc<M, R> p;
+  I2C_HD inline void operator()(const R* x, const R* sn, const R* cs, R* y) const {
+    if constexpr (is_per_traj<M>::value) {
+      R pb[M::NP];
+      M::measure(param_ptr<M::NP>(p, pb), x, sn, cs, y);
+    } else {
+      M::measure(p, x, sn, cs, y);
+    }
+  }
 };
 // dynamics as a function of the state only, with a known action appended (CKF prediction, mpc.py:129-131)
 template <class M, typename R> struct DynamicsFixedUF {
-  const R* p;
+  ParamSrc<M, R> p;
   const R* u;
   I2C_HD inline void operator()(const R* x, const R* sn, const R* cs, R* y) const {
     R xu[M::NX + M::NU];
@@ -87,13 +142,23 @@ template <class M, typename R> struct DynamicsFixedUF {
     for (int i = 0; i < M::NX; ++i) xu[i] = x[i];
 #pragma unroll
     for (int i = 0; i < M::NU; ++i) xu[M::NX + i] = u[i];
-    M::dynamics(p, xu, sn, cs, y);
+    if constexpr (is_per_traj<M>::value) {
+      R pb[M::NP];
+      M::dynamics(param_ptr<M::NP>(p, pb), xu, sn, cs, y);
+    } else {
+      M::dynamics(p, xu, sn, cs, y);
+    }
   }
 };
 template <class M, typename R> struct ObserveTermF {
-  const R* p;
+  ParamSrc<M, R> p;
   I2C_HD inline void operator()(const R* x, const R* sn, const R* cs, R* y) const {
-    M::observe_terminal(p, x, sn, cs, y);
+    if constexpr (is_per_traj<M>::value) {
+      R pb[M::NP];
+      M::observe_terminal(param_ptr<M::NP>(p, pb), x, sn, cs, y);
+    } else {
+      M::observe_terminal(p, x, sn, cs, y);
+    }
   }
 };
 
@@ -809,7 +874,7 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
       }
       const R* L = STRUCT_L0 ? L0 : Lf;
       R mz[NZ], Sz[sym(NZ)], Sxz[D * NZ];
-      transform<GRID, M, ObsStruct<M>, D, NZ, true, LEAN>(c.rule_xu, mu0, S0, L, ObserveF<M, R>{c.params}, mz, Sz, Sxz, tab);
+      transform<GRID, M, ObsStruct<M>, D, NZ, true, LEAN>(c.rule_xu, mu0, S0, L, ObserveF<M, R>{params_of(c, b)}, mz, Sz, Sxz, tab);
 #pragma unroll
       for (int i = 0; i < sym(NZ); ++i) Sz[i] += alpha * (CONST_V ? xi0_v[i] : c.sig_xi0[i + kz]);
       cell_bad = flag_stage(cell_bad, kalman_update<D, NZ>(mu0, S0, mz, Sz, Sxz, zt), 2);
@@ -833,7 +898,7 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
 #pragma unroll
       for (int i = 0; i < sym(D); ++i) L[i] = S0[i];
       cell_bad = flag_stage(cell_bad, chol<D>(L, rinv), 3);
-      transform<GRID, M, DenseStruct<D>, D, NX, true, LEAN>(c.rule_xu, mu0, S0, L, DynamicsF<M, R>{c.params}, mu_x, sig_x, Sxy, tab);
+      transform<GRID, M, DenseStruct<D>, D, NX, true, LEAN>(c.rule_xu, mu0, S0, L, DynamicsF<M, R>{params_of(c, b)}, mu_x, sig_x, Sxy, tab);
     }
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) sig_x[i] += CONST_V ? eta_v[i] : (LEAN ? c.sig_eta[i + kz] : c.sig_eta_w[i + kz]);  // sum_p w_p sig_eta (quadrature.py:57)
@@ -877,7 +942,7 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
     if (NZT > 0 && t == c.terminal_cell && c.has_Qf) {
       constexpr int NT = C::NZT1;
       R mzt[NT], Szt[sym(NT)], Sxzt[NX * NT];
-      transform<GRID, M, TermStruct<M>, NX, NT, true, LEAN>(c.rule_x, mu_x, sig_x, L3, ObserveTermF<M, R>{c.params}, mzt, Szt, Sxzt);
+      transform<GRID, M, TermStruct<M>, NX, NT, true, LEAN>(c.rule_x, mu_x, sig_x, L3, ObserveTermF<M, R>{params_of(c, b)}, mzt, Szt, Sxzt);
 #pragma unroll
       for (int i = 0; i < sym(NT); ++i) Szt[i] += alpha * c.sig_xiT0[i];
       cell_bad = flag_stage(cell_bad, kalman_update<NX, NT>(mu_x, sig_x, mzt, Szt, Sxzt, c.zg_term), 5);
@@ -1038,7 +1103,7 @@ I2C_FN R terminal_obs_stats(const Consts<M, R>& c, const int b, const R* m3m, co
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) L3[i] = S3m[i];
     if (!chol<NX>(L3, rinv3)) set_status(status, b, 6, c.T - 1);
-    transform<GRID, M, TermStruct<M>, NX, NT, false>(c.rule_x, m3m, S3m, L3, ObserveTermF<M, R>{c.params}, mzt, Szt,
+    transform<GRID, M, TermStruct<M>, NX, NT, false>(c.rule_x, m3m, S3m, L3, ObserveTermF<M, R>{params_of(c, b)}, mzt, Szt,
                                                   (R*)nullptr);
     R tv;
     gaussian_cost<NT>(c.Qf, c.qf_diag != 0, mzt, Szt, c.zg_term, &trT, &tv);
@@ -1058,7 +1123,7 @@ I2C_FN R terminal_obs_stats(const Consts<M, R>& c, const int b, const R* m3m, co
 // In: mu/S = mu_xu1_f / sig_xu1_f, J, dm = mu_x3_m - mu_x3_f, dS = sig_x3_m - sig_x3_f.
 // Out: mu/S = mu_xu0_m / sig_xu0_m, ctl = [K | k | sigK], mz/Sz, cost mean / variance.
 template <class M, typename R, bool GRID = false>
-I2C_FN bool cell_posterior(const Consts<M, R>& c, const R* zt, R* mu, R* S, const R* J, const R* dm, const R* dS,
+I2C_FN bool cell_posterior(const Consts<M, R>& c, const int b, const R* zt, R* mu, R* S, const R* J, const R* dm, const R* dS,
                            R* ctl, R* mz, R* Sz, R* cm, R* cv, const PolyTab<R>* tab = nullptr) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NU = C::NU, NZ = C::NZ, D = C::D;
@@ -1074,7 +1139,7 @@ I2C_FN bool cell_posterior(const Consts<M, R>& c, const R* zt, R* mu, R* S, cons
 #pragma unroll
   for (int e = 0; e < sym(D); ++e) Lm[e] = S[e];
   const bool ok = chol<D>(Lm, rinv);
-  transform<GRID, M, ObsStruct<M>, D, NZ, false>(c.rule_xu, mu, S, Lm, ObserveF<M, R>{c.params}, mz, Sz, (R*)nullptr, tab);
+  transform<GRID, M, ObsStruct<M>, D, NZ, false>(c.rule_xu, mu, S, Lm, ObserveF<M, R>{params_of(c, b)}, mz, Sz, (R*)nullptr, tab);
   gaussian_cost<NZ>(c.QR, c.qr_diag != 0, mz, Sz, zt, cm, cv);
 #pragma unroll
   for (int p = 0; p < NU; ++p) {
@@ -1285,7 +1350,7 @@ I2C_HD inline void backward_cell_body(const Consts<M, R>& c, const CellArgs<R, S
   for (int k = 0; k < NZ; ++k) zt[k] = c.z_per_cell ? a.z[((long)c.row(t) * NZ + k) * B + b] : c.zg[k];
 
   R ctl[C::E_POST - D - sym(D)], mz[NZ], Sz[sym(NZ)], cm, cv;
-  if (!cell_posterior<M, R>(c, zt, mu, S, J, dm, dS, ctl, mz, Sz, &cm, &cv)) set_status(a.status, b, 7, t);
+  if (!cell_posterior<M, R>(c, b, zt, mu, S, J, dm, dS, ctl, mz, Sz, &cm, &cv)) set_status(a.status, b, 7, t);
   store_cell<M, R, S_>(c, a, t, b, mu, S, ctl, mz, Sz, cm, cv);
   if (t == c.T - 1) terminal_obs_stats<M, R>(c, b, m3m, S3m, a.term_stats, a.status);
 }
@@ -1391,7 +1456,7 @@ I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, 
     R* mu = row;
     R* S = row + D;
     R ctl[C::E_POST - D - sym(D)], mz[NZ], Sz[sym(NZ)], cm, cv;
-    if (!cell_posterior<M, R, GRID>(c, zt, mu, S, row + O_J, dm, dS, ctl, mz, Sz, &cm, &cv, tab)) set_status(a.status, b, 7, t);
+    if (!cell_posterior<M, R, GRID>(c, b, zt, mu, S, row + O_J, dm, dS, ctl, mz, Sz, &cm, &cv, tab)) set_status(a.status, b, 7, t);
     store_cell<M, R, S_>(c, a, t, b, mu, S, ctl, mz, Sz, cm, cv, VOFF ? voff : nullptr);
     sum_m += cm;
     sum_v += cv;
@@ -1643,7 +1708,7 @@ I2C_HD inline void chunk_walk_body(const Consts<M, R>& c, const ChunkArgs<R, S_>
     R* mu = row;
     R* S = row + D;
     R ctl[C::E_POST - D - sym(D)], mz[NZ], Sz[sym(NZ)], cm, cv;
-    if (!cell_posterior<M, R, GRID>(c, zt, mu, S, row + O_J, dm, dS, ctl, mz, Sz, &cm, &cv, tab)) set_status(ca.status, b, 7, t);
+    if (!cell_posterior<M, R, GRID>(c, b, zt, mu, S, row + O_J, dm, dS, ctl, mz, Sz, &cm, &cv, tab)) set_status(ca.status, b, 7, t);
     store_cell<M, R, S_>(c, ca, t, b, mu, S, ctl, mz, Sz, cm, cv, VOFF ? voff : nullptr);
     sum_m += cm;
     sum_v += cv;
@@ -1834,13 +1899,13 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
     R zt[NZ], mz[NZ], Sz[sym(NZ)];
 #pragma unroll
     for (int k = 0; k < NZ; ++k) zt[k] = ZPRE ? zt_cur[ZPRE ? k : 0] : (c.z_per_cell ? a.z[((long)c.row(t) * NZ + k) * B + b] : c.zg[k]);
-    transform<GRID, M, ObsStruct<M>, D, NZ, false>(c.rule_xu, mu0, S0, L0, ObserveF<M, R>{c.params}, mz, Sz, (R*)nullptr);
+    transform<GRID, M, ObsStruct<M>, D, NZ, false>(c.rule_xu, mu0, S0, L0, ObserveF<M, R>{params_of(c, b)}, mz, Sz, (R*)nullptr);
     R cm, cv;
     gaussian_cost<NZ>(c.QR, c.qr_diag != 0, mz, Sz, zt, &cm, &cv);
     sum_m += cm;
     sum_v += cv;
 
-    transform<GRID, M, DenseStruct<D>, D, NX, false>(c.rule_xu, mu0, S0, L0, DynamicsF<M, R>{c.params}, mu_x, sig_x, (R*)nullptr);
+    transform<GRID, M, DenseStruct<D>, D, NX, false>(c.rule_xu, mu0, S0, L0, DynamicsF<M, R>{params_of(c, b)}, mu_x, sig_x, (R*)nullptr);
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) sig_x[i] += c.sig_eta_w[i];
 #pragma unroll
@@ -1924,14 +1989,14 @@ I2C_HD inline void ckf_filter_body(const Consts<M, R>& c, const R* sig_zeta, con
   bool ok = chol<NX>(L, rinv);
   // prediction (mpc.py:129-137): x-only sigma points, the action is appended unchanged
   R mf[NX], Sf[sym(NX)];
-  sp_transform<M, DenseStruct<NX>, NX, NX, false>(c.rule_x, mu, S, L, DynamicsFixedUF<M, R>{c.params, u}, mf, Sf,
+  sp_transform<M, DenseStruct<NX>, NX, NX, false>(c.rule_x, mu, S, L, DynamicsFixedUF<M, R>{params_of(c, b), u}, mf, Sf,
                                                   (R*)nullptr);
 #pragma unroll
   for (int i = 0; i < sym(NX); ++i) L[i] = Sf[i] = Sf[i] + c.rule_x.W * c.sig_eta[i];
   ok = chol<NX>(L, rinv) && ok;
   // innovation (mpc.py:139-145): K = sig_xy sig_y^{-1}; mu = mu_f + K (y - mu_y); cov = sig_f - K sig_y K^T
   R my[NY], Sy[sym(NY)], Sxy[NX * NY];
-  sp_transform<M, MeasStruct<M>, NX, NY, true>(c.rule_x, mf, Sf, L, MeasureF<M, R>{c.params}, my, Sy, Sxy);
+  sp_transform<M, MeasStruct<M>, NX, NY, true>(c.rule_x, mf, Sf, L, MeasureF<M, R>{params_of(c, b)}, my, Sy, Sxy);
 #pragma unroll
   for (int i = 0; i < sym(NY); ++i) Sy[i] += sig_zeta[i];
   ok = kalman_update<NX, NY>(mf, Sf, my, Sy, Sxy, y) && ok;
@@ -1972,6 +2037,9 @@ I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, 
   const long B = c.B, N = (long)a.n_rollouts * B;
   const int b = n % c.B;
   const int T = c.T;
+  R pb[C::NP1];
+  const R* prm = c.params;
+  if constexpr (is_per_traj<M>::value) prm = param_ptr<M::NP>(params_of(c, b), pb);  // rollout n runs trajectory n % B's plant
   R x[NX];
 #pragma unroll
   for (int i = 0; i < NX; ++i) x[i] = a.x0[i * B + b];
@@ -2042,8 +2110,8 @@ I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, 
     for (int i = 0; i < NU; ++i) xu[NX + i] = u[i];
 #pragma unroll
     for (int q2 = 0; q2 < M::NA; ++q2) r_sincos(xu[M::ang(q2)], &sn[q2], &cs[q2]);
-    M::observe(c.params, xu, sn, cs, zt);
-    M::dynamics(c.params, xu, sn, cs, xn);
+    M::observe(prm, xu, sn, cs, zt);
+    M::dynamics(prm, xu, sn, cs, xn);
     if (a.xu) {
 #pragma unroll
       for (int i = 0; i < D; ++i) a.xu[((long)t * D + i) * N + n] = xu[i];
@@ -2069,7 +2137,7 @@ I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, 
     R sn[NA1], cs[NA1], zT[C::NZT1];
 #pragma unroll
     for (int q2 = 0; q2 < M::NA; ++q2) r_sincos(x[M::ang(q2)], &sn[q2], &cs[q2]);
-    M::observe_terminal(c.params, x, sn, cs, zT);
+    M::observe_terminal(prm, x, sn, cs, zT);
 #pragma unroll
     for (int i = 0; i < NZT; ++i) a.z_term[(long)i * N + n] = zT[i];
   }

@@ -34,6 +34,7 @@ struct ModelOps {
   int (*learn_propagate)(const I2cProblem*, void* post, void* fwd, void* xm, void* zpost, void* cell_stats, void* term_stats, void* prop,
                          void* prop_hist, double tol, int tau, int n_iters, void* stats_hist, int use_expert, int overlap, int32_t* status,
                          void* stream);
+  const ModelOps* per_traj;  // the same entry points with per-trajectory model parameters (I2cProblem.model_params_b); nullptr: NP = 0
 };
 
 // defined by the translation units generated from i2c_model_tu.hip

@@ -901,7 +901,7 @@ I2C_HD inline void forward_group_body(const Consts<M, R>& c, const KC& kc, const
 #pragma unroll
         for (int j = 0; j < D; ++j) L0[j] = s0[j];
         cell_bad = flag_stage(cell_bad, g_chol<D>(g, 0, L0, rinv0), 1);
-        g_transform<M, ObsStruct<M>, D, NZ, true>(g, 0, 1, 2, c.rule_xu, mu0, L0, ObserveF<M, R>{c.params}, mz, szr, sxz);
+        g_transform<M, ObsStruct<M>, D, NZ, true>(g, 0, 1, 2, c.rule_xu, mu0, L0, ObserveF<M, R>{params_of(c, b)}, mz, szr, sxz);
       }
 #pragma unroll
       for (int l = 0; l < NZ; ++l) {
@@ -925,7 +925,7 @@ I2C_HD inline void forward_group_body(const Consts<M, R>& c, const KC& kc, const
       for (int j = 0; j < D; ++j) L1[j] = s0[j];
       cell_bad = flag_stage(cell_bad, g_chol<D>(g, 0, L1, rinv1), 3);
       I2C_STAMP(3);  // stores + chol(sig_xu1_f)
-      g_transform<M, DenseStruct<D>, D, NX, true>(g, 0, 1, 2, c.rule_xu, mu0, L1, DynamicsF<M, R>{c.params}, mu_x, sx, sxy);
+      g_transform<M, DenseStruct<D>, D, NX, true>(g, 0, 1, 2, c.rule_xu, mu0, L1, DynamicsF<M, R>{params_of(c, b)}, mu_x, sx, sxy);
       I2C_STAMP(4);  // dynamics transform
 #pragma unroll
       for (int l = 0; l < NX; ++l) {
@@ -950,7 +950,7 @@ I2C_HD inline void forward_group_body(const Consts<M, R>& c, const KC& kc, const
           sztr[k] = sxzt[k] = sx[k < NX ? k : 0];
         }
       } else {  // chol(sig_x3_f) is still in LDS matrix 0 and its row in L3
-        g_transform<M, TermStruct<M>, NX, NT, true>(g, 0, 1, 2, c.rule_x, mu_x, L3, ObserveTermF<M, R>{c.params}, mzt, sztr, sxzt);
+        g_transform<M, TermStruct<M>, NX, NT, true>(g, 0, 1, 2, c.rule_x, mu_x, L3, ObserveTermF<M, R>{params_of(c, b)}, mzt, sztr, sxzt);
       }
 #pragma unroll
       for (int l = 0; l < NT; ++l) {
@@ -1030,7 +1030,7 @@ I2C_HD inline void backward_group_body(const Consts<M, R>& c, const KC& kc, cons
 #pragma unroll
       for (int j = 0; j < NX; ++j) L3[j] = s3m[j];
       if (!g_chol<NX>(g, 0, L3, rinv3) && r == 0) set_status(a.status, b, 6, T - 1);
-      g_transform<M, TermStruct<M>, NX, NT, false>(g, 0, 1, 2, c.rule_x, m3m, L3, ObserveTermF<M, R>{c.params}, mzt, sztr, (R*)nullptr);
+      g_transform<M, TermStruct<M>, NX, NT, false>(g, 0, 1, 2, c.rule_x, m3m, L3, ObserveTermF<M, R>{params_of(c, b)}, mzt, sztr, (R*)nullptr);
     }
     R tv;
     // FULLW: the instantiation for non-diagonal weights (a compile-time variant: in one kernel the general form's live state
@@ -1187,7 +1187,7 @@ I2C_HD inline void backward_group_body(const Consts<M, R>& c, const KC& kc, cons
         szr[k] = S[k < D ? k : 0];
       }
     } else {
-      g_transform<M, ObsStruct<M>, D, NZ, false>(g, 0, 1, 2, c.rule_xu, mu, Lm, ObserveF<M, R>{c.params}, mz, szr, (R*)nullptr);
+      g_transform<M, ObsStruct<M>, D, NZ, false>(g, 0, 1, 2, c.rule_xu, mu, Lm, ObserveF<M, R>{params_of(c, b)}, mz, szr, (R*)nullptr);
     }
     if constexpr (FULLW) g_cost_full<NZ>(g, kc.qr, mz, szr, zt, &cm, &cv);
     else g_cost<NZ>(g, kc.qr_d, mz, szr, zt, &cm, &cv);
@@ -1324,14 +1324,14 @@ I2C_HD inline void propagate_group_body(const Consts<M, R>& c, const KC& kc, con
       }
     } else {
       // writes LDS matrices 1 and 2 only: the factor in matrix 0 stays for the dynamics transform below
-      g_transform<M, ObsStruct<M>, D, NZ, false>(g, 0, 1, 2, c.rule_xu, mu0, L0, ObserveF<M, R>{c.params}, mz, szr, (R*)nullptr);
+      g_transform<M, ObsStruct<M>, D, NZ, false>(g, 0, 1, 2, c.rule_xu, mu0, L0, ObserveF<M, R>{params_of(c, b)}, mz, szr, (R*)nullptr);
     }
     if constexpr (FULLW) g_cost_full<NZ>(g, kc.qr, mz, szr, zt, &cm, &cv);
     else g_cost<NZ>(g, kc.qr_d, mz, szr, zt, &cm, &cv);
     sum_m += cm;
     sum_v += cv;
 
-    g_transform<M, DenseStruct<D>, D, NX, false>(g, 0, 1, 2, c.rule_xu, mu0, L0, DynamicsF<M, R>{c.params}, mu_x, sx, (R*)nullptr);
+    g_transform<M, DenseStruct<D>, D, NX, false>(g, 0, 1, 2, c.rule_xu, mu0, L0, DynamicsF<M, R>{params_of(c, b)}, mu_x, sx, (R*)nullptr);
 #pragma unroll
     for (int l = 0; l < NX; ++l) sx[l] += c.rule_xu.W * kc.sig_eta[rx * NX + l];
     out.st_if(r < NX, O_X3 + r, g_sel<NX>(mu_x, r));
@@ -1377,7 +1377,7 @@ I2C_HD inline void ckf_group_body(const Consts<M, R>& c, const KC& kc, const Ckf
   bool ok = g_chol<NX>(g, 0, L, rinv);
   // prediction (mpc.py:129-137): x-only sigma points, the action is appended unchanged
   R mf[NX], Sf[NX];
-  g_transform<M, DenseStruct<NX>, NX, NX, false>(g, 0, 1, 2, c.rule_x, mu, L, DynamicsFixedUF<M, R>{c.params, u}, mf, Sf, (R*)nullptr);
+  g_transform<M, DenseStruct<NX>, NX, NX, false>(g, 0, 1, 2, c.rule_x, mu, L, DynamicsFixedUF<M, R>{params_of(c, b), u}, mf, Sf, (R*)nullptr);
 #pragma unroll
   for (int l = 0; l < NX; ++l) L[l] = Sf[l] = Sf[l] + c.rule_x.W * kc.sig_eta[rx * NX + l];
   // innovation (mpc.py:139-145)
@@ -1390,7 +1390,7 @@ I2C_HD inline void ckf_group_body(const Consts<M, R>& c, const KC& kc, const Ckf
     }
   } else {
     ok = g_chol<NX>(g, 0, L, rinv) && ok;
-    g_transform<M, MeasStruct<M>, NX, NY, true>(g, 0, 1, 2, c.rule_x, mf, L, MeasureF<M, R>{c.params}, my, Syr, Sxy);
+    g_transform<M, MeasStruct<M>, NX, NY, true>(g, 0, 1, 2, c.rule_x, mf, L, MeasureF<M, R>{params_of(c, b)}, my, Syr, Sxy);
   }
 #pragma unroll
   for (int l = 0; l < NY; ++l) {

@@ -889,6 +889,7 @@ template <class M, typename R> static Consts<M, R> make_consts(const I2cProblem*
   for (int i = 0; i < C::NX; ++i) c.mu_x_term[i] = (R)p->mu_x_term[i];
   for (int i = 0; i < sym(C::NX); ++i) c.sig_x_term[i] = (R)p->sig_x_term[i];
   for (int i = 0; i < M::NP; ++i) c.params[i] = (R)p->model_params[i];
+  if constexpr (is_per_traj<M>::value) c.params_b = (const R*)p->model_params_b;
   return c;
 }
 
@@ -1728,12 +1729,19 @@ template <class M> static void fill_dims(I2cDims* d) {
   d->quad = M::QUAD ? 1 : 0;
 }
 
-template <class M, typename R, typename S = R> const ModelOps* make_ops() {
+// per_traj: the table of Impl<PerTraj<M>, R, S> (per-trajectory parameters, I2cProblem.model_params_b; i2c_capi.hip switches to it when the
+// pointer is set), built in a translation unit of its own (i2c_model_tu.hip); nullptr for a model without parameters and in that table
+template <class M, typename R, typename S = R> const ModelOps* make_ops(const ModelOps* per_traj) {
   using I = Impl<M, R, S>;
   static const ModelOps ops = {&I::forward, &I::backward,  &I::mstep,        &I::learn,           &I::ckf,
                                &I::rollout, &I::propagate, &I::riccati,   &I::mpc_step,        &fill_dims<M>,
-                               &workspace_elems<M>, &I::plan, &I::shift, &I::family_of, &I::learn_propagate};
+                               &workspace_elems<M>, &I::plan, &I::shift, &I::family_of, &I::learn_propagate, per_traj};
   return &ops;
+}
+// ... the per-trajectory table itself: only models with parameters have one
+template <class M, typename R, typename S = R> const ModelOps* make_per_traj_ops() {
+  if constexpr (M::NP > 0) return make_ops<PerTraj<M>, R, S>(nullptr);
+  else return nullptr;
 }
 
 }  // namespace i2c

@@ -57,7 +57,7 @@ template <class M, int FN, typename T> I2C_FN void call_model(const T* p, const 
   if (FN == FN_OBSERVE_TERMINAL) M::observe_terminal(p, x, sn, cs, y);
 }
 
-// y = f(m) and Jac[k * DIN + j] = d y_k / d m_j for one of the model callbacks.
+// y = f(m) and Jac[k * DIN + j] = d y_k / d m_j for one of the model callbacks (parameters: params_of(), i2c_cell.hpp).
 template <class M, int FN, int DIN, int DOUT, typename R>
 I2C_FN void value_and_jacobian(const R* params, const R* m, R* y, R* Jac) {
   constexpr int NA = M::NA > 0 ? M::NA : 1, NP1 = M::NP > 0 ? M::NP : 1;
@@ -83,6 +83,11 @@ I2C_FN void value_and_jacobian(const R* params, const R* m, R* y, R* Jac) {
     for (int k = 0; k < DOUT; ++k) Jac[k * DIN + j] = yy[k].d;
   }
 }
+template <class M, int FN, int DIN, int DOUT, typename R>
+I2C_FN void value_and_jacobian(const ParamCol<R>& ps, const R* m, R* y, R* Jac) {
+  R pb[M::NP];
+  value_and_jacobian<M, FN, DIN, DOUT, R>((const R*)param_ptr<M::NP>(ps, pb), m, y, Jac);
+}
 
 // Linearised Gaussian push-through: my = f(m), Sxy = Sin Jac^T [DIN x DOUT], Sy = Jac Sin Jac^T (packed).
 template <class M, int FN, int DIN, int DOUT, typename R>
@@ -106,6 +111,11 @@ I2C_FN void lin_transform(const R* params, const R* m, const R* Sin, R* my, R* S
       for (int i = 0; i < DIN; ++i) v += Jac[k * DIN + i] * Sxy[i * DOUT + l];
       Sy[tri(k, l)] = v;
     }
+}
+template <class M, int FN, int DIN, int DOUT, typename R>
+I2C_FN void lin_transform(const ParamCol<R>& ps, const R* m, const R* Sin, R* my, R* Sy, R* Sxy, R* Jac) {
+  R pb[M::NP];
+  lin_transform<M, FN, DIN, DOUT, R>((const R*)param_ptr<M::NP>(ps, pb), m, Sin, my, Sy, Sxy, Jac);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -232,7 +242,7 @@ I2C_HD inline void forward_lin_body(const Consts<M, R>& c, const FwdArgs<R>& a, 
     // ---- 2. cost observation linearised about the prior mean (i2c.py:281-305) ----
     {
       R mz[NZ], Sz[sym(NZ)], Sxz[D * NZ], EF[NZ * D];
-      lin_transform<M, FN_OBSERVE, D, NZ, R>(c.params, mu0, S0, mz, Sz, Sxz, EF);
+      lin_transform<M, FN_OBSERVE, D, NZ, R>(params_of(c, b), mu0, S0, mz, Sz, Sxz, EF);
 #pragma unroll
       for (int i = 0; i < sym(NZ); ++i) Sz[i] += alpha * c.sig_xi0[i];
       fail = note_failure(fail, kalman_update<D, NZ>(mu0, S0, mz, Sz, Sxz, zt), 3, t);
@@ -246,7 +256,7 @@ I2C_HD inline void forward_lin_body(const Consts<M, R>& c, const FwdArgs<R>& a, 
     R Sxy[D * NX];
     {
       R AB[NX * D];
-      lin_transform<M, FN_DYNAMICS, D, NX, R>(c.params, mu0, S0, mu_x, sig_x, Sxy, AB);
+      lin_transform<M, FN_DYNAMICS, D, NX, R>(params_of(c, b), mu0, S0, mu_x, sig_x, Sxy, AB);
     }
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) sig_x[i] += c.sig_eta[i];
@@ -306,7 +316,7 @@ I2C_FN void lin_end_of_chain(const Consts<M, R>& c, const CellArgs<R>& a, const 
       // Szx = E S3f and MP = Szx Szx^T,  sig_z = MP (Szx (S3f - S_T) Szx^T)^-1 MP  and  sig_xi_terminal = sig_z - E S3f E^T
       // (the middle factor is symmetric but in general indefinite: chol_signed)
       R mzt[NT], Szt[sym(NT)], Sxzt[NX * NT], E[NT * NX], W[NX * NT], mid[sym(NT)], rinv[NT], sgn[NT], Y[NT * NT];
-      lin_transform<M, FN_OBSERVE_TERMINAL, NX, NT, R>(c.params, m3m, S3m, mzt, Szt, Sxzt, E);
+      lin_transform<M, FN_OBSERVE_TERMINAL, NX, NT, R>(params_of(c, b), m3m, S3m, mzt, Szt, Sxzt, E);
 #pragma unroll
       for (int i = 0; i < NX; ++i)
 #pragma unroll
@@ -348,7 +358,7 @@ I2C_FN void lin_end_of_chain(const Consts<M, R>& c, const CellArgs<R>& a, const 
     for (int i = 0; i < sym(NX); ++i) S3m[i] = c.sig_x_term[i];
   } else if (NZT > 0 && c.has_Qf) {
     R mzt[NT], Szt[sym(NT)], Sxzt[NX * NT], E[NT * NX];
-    lin_transform<M, FN_OBSERVE_TERMINAL, NX, NT, R>(c.params, m3m, S3m, mzt, Szt, Sxzt, E);
+    lin_transform<M, FN_OBSERVE_TERMINAL, NX, NT, R>(params_of(c, b), m3m, S3m, mzt, Szt, Sxzt, E);
 #pragma unroll
     for (int i = 0; i < sym(NT); ++i) {
       xiT[i] = alpha * c.sig_xiT0[i];
@@ -358,7 +368,7 @@ I2C_FN void lin_end_of_chain(const Consts<M, R>& c, const CellArgs<R>& a, const 
   }
   if (NZT > 0 && c.has_Qf) {  // mu_z3_m, sig_z3_m = E sig_x3_m E^T + sig_xi_terminal (i2c.py:499-501), alpha statistic :989-992
     R mzt[NT], Szt[sym(NT)], Sxzt[NX * NT], E[NT * NX], tv;
-    lin_transform<M, FN_OBSERVE_TERMINAL, NX, NT, R>(c.params, m3m, S3m, mzt, Szt, Sxzt, E);
+    lin_transform<M, FN_OBSERVE_TERMINAL, NX, NT, R>(params_of(c, b), m3m, S3m, mzt, Szt, Sxzt, E);
 #pragma unroll
     for (int i = 0; i < sym(NT); ++i) Szt[i] += xiT[i];
     gaussian_cost<NT>(c.Qf, c.qf_diag != 0, mzt, Szt, c.zg_term, &trT, &tv);
@@ -404,11 +414,11 @@ I2C_FN void lin_backward_cell(const Consts<M, R>& c, const CellArgs<R>& a, const
 
     // RTS update, controller and the cubature cost of the posterior (shared with the sigma-point path)
     R ctl[C::E_POST - D - sym(D)], mzq[NZ], Szq[sym(NZ)], cm, cv;
-    if (!cell_posterior<M, R>(c, zt, mu, S, J, dm, dS, ctl, mzq, Szq, &cm, &cv)) set_status(a.status, b, 7, t);
+    if (!cell_posterior<M, R>(c, b, zt, mu, S, J, dm, dS, ctl, mzq, Szq, &cm, &cv)) set_status(a.status, b, 7, t);
 
     // linearised marginal observation (i2c.py:537-540): block-diagonal use of the posterior covariance
     R mz[NZ], Sz[sym(NZ)], CD[NZ * D];
-    value_and_jacobian<M, FN_OBSERVE, D, NZ, R>(c.params, mu, mz, CD);
+    value_and_jacobian<M, FN_OBSERVE, D, NZ, R>(params_of(c, b), mu, mz, CD);
 #pragma unroll
     for (int k = 0; k < NZ; ++k)
 #pragma unroll
@@ -756,7 +766,7 @@ I2C_HD inline void riccati_body(const Consts<M, R>& c, const RiccatiArgs<R>& a, 
 
     // observation linearised about the prior mean (i2c.py:281-294, 312-317)
     R mz[NZ], EF[NZ * D], E[NZ * NX], F[NZ * NU], ev[NZ];
-    value_and_jacobian<M, FN_OBSERVE, D, NZ, R>(c.params, mu0, mz, EF);
+    value_and_jacobian<M, FN_OBSERVE, D, NZ, R>(params_of(c, b), mu0, mz, EF);
 #pragma unroll
     for (int k = 0; k < NZ; ++k) {
       R v = mz[k];
@@ -814,7 +824,7 @@ I2C_HD inline void riccati_body(const Consts<M, R>& c, const RiccatiArgs<R>& a, 
     }
     // dynamics linearised about the updated mean (i2c.py:321-332)
     R f1[NX], AB[NX * D], Am[NX * NX], Bm[NX * NU], av[NX];
-    value_and_jacobian<M, FN_DYNAMICS, D, NX, R>(c.params, mu1, f1, AB);
+    value_and_jacobian<M, FN_DYNAMICS, D, NX, R>(params_of(c, b), mu1, f1, AB);
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
       R v = f1[i];

@@ -433,10 +433,15 @@ I2C_FN void q_elim2(const Quad<R>& q, R* sa, R* ra1, R* ra2, R* lta, bool* oka, 
 
 // observe() without its last outputs (LASTLIN, forward_quad_body): the first NOUT of them
 template <class M, typename R, int NOUT> struct ObserveHeadF {
-  const R* p;
+  ParamSrc<M, R> p;
   I2C_HD inline void operator()(const R* x, const R* sn, const R* cs, R* y) const {
     R yy[M::NZ];
-    M::observe(p, x, sn, cs, yy);
+    if constexpr (is_per_traj<M>::value) {
+      R pb[M::NP];
+      M::observe(param_ptr<M::NP>(p, pb), x, sn, cs, yy);
+    } else {
+      M::observe(p, x, sn, cs, yy);
+    }
 #pragma unroll
     for (int k = 0; k < NOUT; ++k) y[k] = yy[k];
   }
@@ -1233,7 +1238,7 @@ I2C_HD inline void forward_quad_body(const Consts<M, R>& c, const KC& kc, const 
       I2C_QSTAMP(1);
       constexpr int NZ8 = NZ - 1, NB8 = NZ8 / 4, BJ = JZL / 4, CZ = JZL % 4;
       R am[NBD * NB8], dm[NBD * NB8], yc[NB8], mz[NB8], sz[NB8 * NB8], szx[NB8 * NBD];
-      q_points<M, G, D, NZ8>(q, rule.sf, mu0, lt0, ObserveHeadF<M, R, NZ8>{c.params}, am, dm, yc);
+      q_points<M, G, D, NZ8>(q, rule.sf, mu0, lt0, ObserveHeadF<M, R, NZ8>{params_of(c, b)}, am, dm, yc);
       I2C_QSTAMP(2);  // observation points
       q_moments<D, NZ8>(q, rule, am, dm, yc, mz, sz);
 #pragma unroll
@@ -1285,7 +1290,7 @@ I2C_HD inline void forward_quad_body(const Consts<M, R>& c, const KC& kc, const 
     } else {
       I2C_QSTAMP(1);
       R am[NBD * NBZ], dm[NBD * NBZ], yc[NBZ], mz[NBZ], sz[NBZ * NBZ], szx[NBZ * NBD];
-      q_points<M, G, D, NZ>(q, rule.sf, mu0, lt0, ObserveF<M, R>{c.params}, am, dm, yc);
+      q_points<M, G, D, NZ>(q, rule.sf, mu0, lt0, ObserveF<M, R>{params_of(c, b)}, am, dm, yc);
       I2C_QSTAMP(2);  // observation points
       q_moments<D, NZ, GENERAL>(q, rule, am, dm, yc, mz, sz);
 #pragma unroll
@@ -1324,7 +1329,7 @@ I2C_HD inline void forward_quad_body(const Consts<M, R>& c, const KC& kc, const 
       }
       I2C_QSTAMP(5);  // stores + chol(updated joint)
       R am[NBD * NBX], dm[NBD * NBX], yc[NBX], sy[NBX * NBX];
-      q_points<M, G, D, NX, CENTRE>(q, rule.sf, mu0, lt, DynamicsF<M, R>{c.params}, am, dm, yc);
+      q_points<M, G, D, NX, CENTRE>(q, rule.sf, mu0, lt, DynamicsF<M, R>{params_of(c, b)}, am, dm, yc);
       I2C_QSTAMP(6);  // dynamics points
       q_moments<D, NX, GENERAL>(q, rule, am, dm, yc, mx, sy);
 #pragma unroll
@@ -1369,7 +1374,7 @@ I2C_HD inline void forward_quad_body(const Consts<M, R>& c, const KC& kc, const 
           for (int j = 0; j < NBX; ++j) sx[i * NBX + j] = j >= i ? sf_[i * NBX + j] : R(0);
       } else if constexpr (NZT > 0) {
         R am[NBX * NBT], dm[NBX * NBT], yc[NBT], mz[NBT], sz[NBT * NBT], szx[NBT * NBX];
-        q_points<M, G, NX, NT>(q, c.rule_x.sf, mx, l3t, ObserveTermF<M, R>{c.params}, am, dm, yc);
+        q_points<M, G, NX, NT>(q, c.rule_x.sf, mx, l3t, ObserveTermF<M, R>{params_of(c, b)}, am, dm, yc);
         q_moments<NX, NT, GENERAL>(q, c.rule_x, am, dm, yc, mz, sz);
 #pragma unroll
         for (int i = 0; i < NBT; ++i)
@@ -2106,7 +2111,7 @@ I2C_HD inline void backward_quad8_body(const Consts<M, R>& c, const KC& kc, cons
 #pragma unroll
         for (int k = 0; k < NBX * NBX; ++k) tmp[k] = s3m[k];
         note(q_elim<NX, 0, 0>(q, tmp, (R*)nullptr, (R*)nullptr, l3t), 6, T - 1);
-        q_points<M, G, NX, NT>(q, c.rule_x.sf, m3m, l3t, ObserveTermF<M, R>{c.params}, am, dm, yc);
+        q_points<M, G, NX, NT>(q, c.rule_x.sf, m3m, l3t, ObserveTermF<M, R>{params_of(c, b)}, am, dm, yc);
         q_moments<NX, NT, GENERAL>(q, c.rule_x, am, dm, yc, mzt, szt);
 #pragma unroll
         for (int j = 0; j < NBT; ++j) errT[j] = mzt[j] - q_ldv(q, kc.zgT, j, kz);
@@ -2307,7 +2312,7 @@ I2C_HD inline void backward_quad8_body(const Consts<M, R>& c, const KC& kc, cons
         }
       } else {
         R am[NBD * NBZ], dm[NBD * NBZ], yc[NBZ], mz[NBZ], sz[NBZ * NBZ], err[NBZ];
-        q_points<M, G, D, NZ>(q, rule.sf, mu, lt, ObserveF<M, R>{c.params}, am, dm, yc);
+        q_points<M, G, D, NZ>(q, rule.sf, mu, lt, ObserveF<M, R>{params_of(c, b)}, am, dm, yc);
         q_moments<D, NZ, GENERAL>(q, rule, am, dm, yc, mz, sz);
 #pragma unroll
         for (int j = 0; j < NBZ; ++j) err[j] = mz[j] - zt[j];
@@ -2561,7 +2566,7 @@ I2C_HD inline void ckf_quad_body(const Consts<M, R>& c, const KC& kc, const CkfA
 #pragma unroll
     for (int k = 0; k < NBX * NBX; ++k) tmp[k] = S[k];
     ok = q_elim<NX, 0, 0>(q, tmp, (R*)nullptr, (R*)nullptr, lt);
-    q_points<M, G, NX, NX>(q, rule.sf, mu, lt, DynamicsFixedUF<M, R>{c.params, u}, am, dm, yc);
+    q_points<M, G, NX, NX>(q, rule.sf, mu, lt, DynamicsFixedUF<M, R>{params_of(c, b), u}, am, dm, yc);
     q_moments<NX, NX>(q, rule, am, dm, yc, mf, Sf);
 #pragma unroll
     for (int i = 0; i < NBX; ++i)
@@ -2574,7 +2579,7 @@ I2C_HD inline void ckf_quad_body(const Consts<M, R>& c, const KC& kc, const CkfA
 #pragma unroll
     for (int k = 0; k < NBX * NBX; ++k) tmp[k] = Sf[k];
     ok = q_elim<NX, 0, 0>(q, tmp, (R*)nullptr, (R*)nullptr, lt) && ok;
-    q_points<M, G, NX, NY>(q, rule.sf, mf, lt, MeasureF<M, R>{c.params}, am, dm, yc);
+    q_points<M, G, NX, NY>(q, rule.sf, mf, lt, MeasureF<M, R>{params_of(c, b)}, am, dm, yc);
     q_moments<NX, NY>(q, rule, am, dm, yc, my, Sy);
 #pragma unroll
     for (int i = 0; i < NBY; ++i)
@@ -2823,7 +2828,7 @@ I2C_HD inline void propagate_quad_body(const Consts<M, R>& c, const KC& kc, cons
 #pragma unroll
       for (int k = 0; k < NBD * NBD; ++k) tmp[k] = s0[k];
       note(q_elim<D, 0, 0>(q, tmp, (R*)nullptr, (R*)nullptr, lt), t);
-      q_points<M, G, D, NX, GENERAL>(q, rule.sf, mu0, lt, DynamicsF<M, R>{c.params}, am, dm, yc);  // (d = 16: no spare pair row, the centre is an extra pass)
+      q_points<M, G, D, NX, GENERAL>(q, rule.sf, mu0, lt, DynamicsF<M, R>{params_of(c, b)}, am, dm, yc);  // (d = 16: no spare pair row, the centre is an extra pass)
       q_moments<D, NX, GENERAL>(q, rule, am, dm, yc, mx, sy);
 #pragma unroll
       for (int i = 0; i < NBX; ++i)

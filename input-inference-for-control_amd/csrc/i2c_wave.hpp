@@ -724,7 +724,12 @@ I2C_HD inline void forward_wave_body(const Consts<M, R>& c, const KC& kc, const 
         for (int i = 0; i < D; ++i) x[i] = mv[i] + sg * Lt[p * WLD + i];
 #pragma unroll
         for (int k = 0; k < M::NA; ++k) r_sincos(x[M::ang(k)], &sn[k], &cs[k]);
-        M::dynamics(c.params, x, sn, cs, y);
+        if constexpr (is_per_traj<M>::value) {
+          R pb[M::NP];
+          M::dynamics(param_ptr<M::NP>(params_of(c, b), pb), x, sn, cs, y);
+        } else {
+          M::dynamics(c.params, x, sn, cs, y);
+        }
         const auto Y = w.ybuf();
         if (w.l <= 32) {  // lanes beyond the centre computed a copy of it
 #pragma unroll
@@ -780,8 +785,11 @@ I2C_HD inline void forward_wave_body(const Consts<M, R>& c, const KC& kc, const 
         constexpr int NA1 = M::NA > 0 ? M::NA : 1, NP1 = M::NP > 0 ? M::NP : 1;
         const int p = w.l & 15;
         Dual<R> pd[NP1], x[D], sn[NA1], cs[NA1], y[NX];
+        R pb[NP1];
+        const R* prm = c.params;
+        if constexpr (is_per_traj<M>::value) prm = param_ptr<M::NP>(params_of(c, b), pb);
 #pragma unroll
-        for (int i = 0; i < M::NP; ++i) pd[i] = Dual<R>(c.params[i]);
+        for (int i = 0; i < M::NP; ++i) pd[i] = Dual<R>(prm[i]);
 #pragma unroll
         for (int i = 0; i < D; ++i) x[i] = Dual<R>(mv[i], i == p ? R(1) : R(0));
 #pragma unroll

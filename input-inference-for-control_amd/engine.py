@@ -57,7 +57,7 @@ class BatchedI2c:
                  z_traj=None, batch=None, dtype=torch.float64, device=None, lib=None, dtemp=1.0,
                  keep_zpost=True, keep_prior=False, keep_xm=True, backward_mode="auto", inference="cubature",
                  gh_degree=None, group_lanes=0, storage_dtype=None, allow_inexact=False, keep_prior_joint=False, post_layout=None,
-                 deterministic_family=False, overlap_propagation=True):
+                 deterministic_family=False, overlap_propagation=True, model_params=None):
         self.lib = lib if lib is not None else _native.load_library()
         if device is None:
             device = "cpu" if self.lib.is_host_sim else "cuda"
@@ -291,6 +291,11 @@ class BatchedI2c:
         # batch size, the request); the workspaces and the layout of the forward messages follow from its answers. A problem
         # the library refuses is refused here, with the library's code.
         self.work = None
+        # Per-trajectory model parameters (I2cProblem.model_params_b): None = model.device_params() for every trajectory;
+        # a (B, NP) array = trajectory b's dynamics / observe / measure use row b. Kept on the device as [NP][B] (arithmetic dtype).
+        self._params_b = None
+        if model_params is not None:
+            self._params_b = self._params_to_device(model_params)
         self._problem = self._make_problem()
         mode = self.lib.i2c_backward_schedule(C.byref(self._problem))
         if mode not in (_native.BWD_TWO_PASS, _native.BWD_FUSED, _native.BWD_CHUNKED):
@@ -371,7 +376,35 @@ class BatchedI2c:
         p.work = self.work.data_ptr() if getattr(self, "work", None) is not None else None
         p.feedforward = self.feedforward.data_ptr()
         p.expert = self.expert_cells.data_ptr() if self.expert_cells is not None else None
+        p.model_params_b = self._params_b.data_ptr() if self._params_b is not None else None
         return p
+
+    def _params_to_device(self, params):
+        """(B, NP) array / tensor of per-trajectory model parameters -> a new [NP][B] device tensor in the arithmetic dtype."""
+        n_params = int(self.dims.n_params)
+        if n_params == 0:
+            raise ValueError(f"{type(self.sys).__name__} has no model parameters: there is nothing to vary per trajectory")
+        a = params.detach().to("cpu", torch.float64).numpy() if torch.is_tensor(params) else np.asarray(params, np.float64)
+        if a.shape != (self.B, n_params):
+            raise ValueError(f"model_params must be (B, NP) = ({self.B}, {n_params}), got {a.shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError("model_params must be finite")
+        return torch.as_tensor(np.array(a.T, order="C"), dtype=self.dtype, device=self.device)
+
+    @property
+    def model_params(self):
+        """Per-trajectory model parameters as a (B, NP) tensor, or None when every trajectory uses model.device_params()."""
+        return None if self._params_b is None else self._params_b.T.clone()
+
+    def set_model_params(self, params):
+        """Replace the per-trajectory model parameters, (B, NP), in place (the device pointer stays: a payload that changes
+        between MPC steps needs nothing else). An engine built without model_params gets its buffer here."""
+        v = self._params_to_device(params)
+        if self._params_b is None:
+            self._params_b = v
+            self.refresh_problem()
+        else:
+            self._params_b.copy_(v)
 
     def kernel_family(self, sweep="forward"):
         """Which kernel family serves a sweep of THIS problem ("lane", "group", "wave" or "quad"): i2c_kernel_family(), the library's
@@ -760,11 +793,13 @@ class BatchedI2c:
             self.z.copy_(zt)
 
     def rollout(self, n_rollouts=1, policy="linear", process_noise=True, action_noise=False, sample_x0=False,
-                generator=None, want=("xu", "z", "x_final", "z_term"), eps_x0=None, eps_x=None, eps_u=None):
+                generator=None, want=("xu", "z", "x_final", "z_term"), eps_x0=None, eps_x=None, eps_u=None, model_params=None):
         """Simulate the current controllers through the noisy model (env.batch_eval, i2c/env.py:93-103):
         n_rollouts per trajectory, all B * n_rollouts in one launch. Returns a dict of (R, B, T, ...) tensors.
         The standard-normal disturbances are drawn here (torch.randn) unless given: eps_x0 [nx][N], eps_x [T][nx][N],
-        eps_u [T][nu][N] with N = n_rollouts * B, rollout n = r * B + b."""
+        eps_u [T][nu][N] with N = n_rollouts * B, rollout n = r * B + b.
+        model_params: (B, NP) parameters of the PLANT for this rollout only (rollout n simulates row n % B), e.g. controllers
+        planned on the nominal model evaluated on perturbed ones; None = the planning parameters."""
         N, T, dev, dt = int(n_rollouts) * self.B, self.H, self.device, self.dtype
         code = {"linear": 0, "expert": 1, "expert_soft": 1, "expert_hard": 2}[policy]
         rnd = lambda *s: torch.randn(*s, dtype=dt, device=dev, generator=generator)  # noqa: E731
@@ -778,7 +813,12 @@ class BatchedI2c:
             "x_final": torch.empty(self.nx, N, dtype=dt, device=dev) if "x_final" in want else None,
             "z_term": torch.empty(self.nzt, N, dtype=dt, device=dev) if ("z_term" in want and self.nzt > 0) else None,
         }
-        rc = self.lib.i2c_rollout(C.byref(self._problem), self._ptr(self.post), int(n_rollouts), code, self._ptr(eps_x0),
+        problem, plant = self._problem, None
+        if model_params is not None:
+            plant = self._params_to_device(model_params)
+            problem = self._make_problem()
+            problem.model_params_b = plant.data_ptr()
+        rc = self.lib.i2c_rollout(C.byref(problem), self._ptr(self.post), int(n_rollouts), code, self._ptr(eps_x0),
                                   self._ptr(eps_x), self._ptr(eps_u), self._ptr(out["xu"]), self._ptr(out["z"]),
                                   self._ptr(out["x_final"]), self._ptr(out["z_term"]), self._stream())
         self._check(rc, "i2c_rollout")

@@ -33,7 +33,7 @@ def main():
     pat = sys.argv[4] if len(sys.argv) > 4 else kern
     with tempfile.TemporaryDirectory() as d:
         cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", f"-DI2C_TU_MODEL={model}", "-DI2C_TU_REAL=double",
-               f"-DI2C_TU_OPS=ops_{name}_f64", "-c", os.path.join(ROOT, "input-inference-for-control_amd", "csrc", "i2c_model_tu.hip"),
+               f"-DI2C_TU_OPS=ops_{name}_f64", f"-DI2C_TU_OPS_PT=ops_{name}_f64_pt", "-c", os.path.join(ROOT, "input-inference-for-control_amd", "csrc", "i2c_model_tu.hip"),
                "-o", os.path.join(d, "x.o"), "-save-temps=obj"]
         subprocess.run(cmd, check=True, capture_output=True, cwd=d)
         lines = open(os.path.join(d, "i2c_model_tu-hip-amdgcn-amd-amdhsa-gfx950.s")).read().split("\n")
