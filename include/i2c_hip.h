@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define I2C_ABI_VERSION 8
+#define I2C_ABI_VERSION 9
 
 #define I2C_MAX_NX 12
 #define I2C_MAX_NU 4
@@ -491,6 +491,76 @@ int i2c_rollout(const I2cProblem* p, const void* post, int n_rollouts, int polic
  */
 int i2c_ckf_filter(const I2cProblem* p, const double* sig_zeta, const void* y, const void* u, void* mu,
                    void* cov, int32_t* status, void* stream);
+
+/*
+ * One step of the noisy PLANT under the action a control step planned: replaces the host code between two calls of the policy
+ * in the reference's closed loop (scripts/mpc_state_est/mpc_quad.py:643-660: env.step :414-420, the measurement :408-412 and the
+ * tracking cost :659-660). One lane per trajectory:
+ *   cost[b] += (z - z_ref)^T QR (z - z_ref),  z = sys.observe(x, u)
+ *   x <- sys.forward(x, u) + chol(sig_eta) eps_x          (the model clips the action itself)
+ *   y_out <- sys.measure(x) + chol(sig_zeta) eps_y        (skipped when y_out is NULL)
+ *   x_obs <- x                                             (skipped when x_obs is NULL)
+ *   sig_zeta  HOST [SYM(ny)] double, or NULL when eps_y is NULL
+ *   x [nx][B] in/out; u [nu][B] in: e.g. the first nu rows of I2cMpcStep.action
+ *   eps_x [nx][B], eps_y [ny][B]: standard-normal samples, each optional (NULL: no noise of that kind) -- as in i2c_rollout the
+ *             step is a deterministic function of its inputs; I2C_EINVAL when a sample is given and its covariance is not
+ *             positive definite
+ *   y_out [ny][B] optional: the measurement the next filter step reads
+ *   x_obs [nx][B] optional: receives the new state -- hand it p->x0 for a fully observed loop (MpcPolicy.__call__(i, x),
+ *             i2c/policy/mpc.py:95-111)
+ *   z_ref [nz][B] optional: the cost reference (NULL: p->zg);  cost [B] optional, ACCUMULATED
+ * The plant is the problem's model: p->model_params, or column b of p->model_params_b -- a caller whose plant differs from the
+ * planner's model passes a copy of the problem with the plant's parameters. Of the problem only model_id, dtype, B, sig_eta, QR,
+ * zg and the parameters are read, and only its SCALAR fields are checked (what i2c_kernel_family checks: abi_version, B, T, t0,
+ * inference, post_layout, model_params_b on a model without parameters): the problem's device buffers need not exist.
+ * The action is taken as planned: the model's dynamics clip it to the actuator limits themselves (and so does the dynamics of
+ * the next filter step), but z = sys.observe(x, u) -- hence the cost -- sees the UNCLIPPED u, where the reference's loop clips
+ * first and prices the clipped action (mpc_quad.py:645-647, 659). The two agree whenever the plan respects the limits; a caller
+ * who wants the reference's figure while the clip is active clips u before the call.
+ */
+int i2c_plant_step(const I2cProblem* p, const double* sig_zeta, void* x, const void* u, const void* eps_x, const void* eps_y,
+                   void* y_out, void* x_obs, const void* z_ref, void* cost, void* stream);
+
+/*
+ * A closed-loop MPC EPISODE with no host round trip: n_steps control steps enqueued back to back, each followed by a plant step.
+ * Replaces the loop of scripts/mpc_state_est/mpc_quad.py:643-660 around PartiallyObservedMpcPolicy.__call__ / MpcPolicy.__call__:
+ *   for k = 0 .. n_steps - 1:
+ *     i2c_mpc_step  -- partially observed: with the filter step on (y, u) from k >= 1 on (mpc.py:156-158);
+ *                      fully observed (observe_state): never a filter step, the belief mean p->x0 is the plant's state;
+ *                      target of the appended cell: row min(k + T, n_z - 1) of z_traj (mpc.py:177-181; NULL: the last cell's)
+ *     plant step    -- as i2c_plant_step on x_true with the action just planned; cost reference: row min(k, n_z - 1) of z_traj
+ *                      (NULL: p->zg); writes y and u for the next control step (observe_state: p->x0 <- x_true)
+ *   the ring advances on the call's own copy of the problem: t0 += 1 (mod T), terminal_cell -= 1 while it is >= 0;
+ *   the final values are REPORTED in t0_out / terminal_cell_out and belong into the caller's problem before its next call.
+ * `step` supplies what every control step shares: n_iter, tau, sig_zeta, post .. term_stats, cell_init, alpha_init, action
+ * (required here: the plant reads it) and status; its do_filter, y, u and z_new are ignored (the episode sets them per step).
+ * The plan starts from the belief in p->x0 / p->sig_x0; the first control step never filters.
+ * u_hist, the u handed to the next filter step and the cost are of the action AS PLANNED (unclipped; see i2c_plant_step).
+ * Numerical failures stay per trajectory in status[b] (first failing step, as everywhere): the batch goes on, a failed
+ * trajectory's plant keeps stepping on whatever its action row holds (NaN as a rule, so its x_true, histories and cost go
+ * non-finite and say so), and no other trajectory reads anything of it.
+ */
+typedef struct I2cEpisode {
+  int32_t n_steps;        /* N >= 0 */
+  int32_t observe_state;  /* 0: partially observed (filter on the measurement); 1: fully observed */
+  int32_t n_z;            /* rows of z_traj (>= 1 when z_traj is given) */
+  int32_t t0_out, terminal_cell_out; /* OUT: I2cProblem.t0 / terminal_cell after the episode */
+  int32_t reserved0;
+  void* x_true;           /* [nx][B] in/out: the plants' states */
+  const void* eps_x;      /* [N][nx][B] or NULL: process noise samples */
+  const void* eps_y;      /* [N][ny][B] or NULL: measurement noise samples */
+  const void* plant_params_b; /* optional [NP][B]: the PLANTS' parameters when they differ from the planner's model
+                                 (p->model_params / p->model_params_b); I2C_EINVAL on a model with n_params = 0 */
+  const void* z_traj;     /* optional [n_z][nz][B]: needs p->z_per_cell */
+  void* y;                /* [ny][B] workspace: the measurement between two steps (may be NULL when observe_state) */
+  void* u;                /* [nu][B] workspace: the applied action between two steps */
+  void* x_hist;           /* optional [N][nx][B]: state BEFORE step k */
+  void* u_hist;           /* optional [N][nu][B]: action of step k */
+  void* y_hist;           /* optional [N][ny][B]: measurement AFTER step k (not in observe_state mode) */
+  void* mu_hist;          /* optional [N][nx][B]: belief mean the plan of step k started from */
+  void* cost;             /* [B] in/out: the stage costs of the steps are ADDED to it (the caller zeroes it; episodes chain) */
+} I2cEpisode;
+int i2c_mpc_episode(const I2cProblem* p, const I2cMpcStep* step, I2cEpisode* ep, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ without a GPU; nothing in the package ever looks for it.)
 import ctypes as C
 import os
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_NX, MAX_NU, MAX_NZ, MAX_PARAMS = 12, 4, 16, 16
 MAX_GH_DEGREE = 8
 
@@ -116,6 +116,16 @@ class I2cMpcStep(C.Structure):
     ]
 
 
+class I2cEpisode(C.Structure):
+    _fields_ = [
+        ("n_steps", C.c_int32), ("observe_state", C.c_int32), ("n_z", C.c_int32), ("t0_out", C.c_int32),
+        ("terminal_cell_out", C.c_int32), ("reserved0", C.c_int32),
+        ("x_true", C.c_void_p), ("eps_x", C.c_void_p), ("eps_y", C.c_void_p), ("plant_params_b", C.c_void_p),
+        ("z_traj", C.c_void_p), ("y", C.c_void_p), ("u", C.c_void_p),
+        ("x_hist", C.c_void_p), ("u_hist", C.c_void_p), ("y_hist", C.c_void_p), ("mu_hist", C.c_void_p), ("cost", C.c_void_p),
+    ]
+
+
 _SIGNATURES = {
     "i2c_abi_version": (C.c_int, []),
     "i2c_problem_size": (C.c_size_t, []),
@@ -148,6 +158,8 @@ _SIGNATURES = {
         C.c_int,
         [C.POINTER(I2cProblem), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     ),
+    "i2c_plant_step": (C.c_int, [C.POINTER(I2cProblem), C.POINTER(C.c_double)] + [C.c_void_p] * 9),
+    "i2c_mpc_episode": (C.c_int, [C.POINTER(I2cProblem), C.POINTER(I2cMpcStep), C.POINTER(I2cEpisode), C.c_void_p]),
     "i2c_propagate": (C.c_int, [C.POINTER(I2cProblem), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 

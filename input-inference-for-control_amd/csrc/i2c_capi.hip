@@ -2,6 +2,7 @@
 // (i2c_model_tu.hip -> i2c_impl.hpp). No kernel code is compiled here.
 #include <dlfcn.h>
 
+#include <cmath>
 #include <mutex>
 
 #include "i2c_entry.hpp"
@@ -240,6 +241,124 @@ int i2c_ckf_filter(const I2cProblem* p, const double* sig_zeta, const void* y, c
                    int32_t* status, void* stream) {
   if (!sig_zeta || !y || !u || !mu || !cov || !status) return I2C_EINVAL;
   I2C_DISPATCH(p, ckf(p, sig_zeta, y, u, mu, cov, status, stream));
+}
+
+}  // extern "C"
+
+namespace {
+
+// packed lower Cholesky factor of a packed symmetric n x n matrix, on the host: the plant's noise covariances are constants of a
+// call, so they are factored here once and travel to the kernel as arguments. false: not positive definite.
+bool chol_packed_host(const double* S, int n, double* L) {
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double v = S[i * (i + 1) / 2 + j];
+      for (int k = 0; k < j; ++k) v -= L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
+      if (i == j) {
+        if (!(v > 0.0)) return false;
+        L[i * (i + 1) / 2 + i] = std::sqrt(v);
+      } else {
+        L[i * (i + 1) / 2 + j] = v / L[j * (j + 1) / 2 + j];
+      }
+    }
+  return true;
+}
+
+// the table that simulates the plant of problem p, and the two noise factors (NULL in `call` where a noise is off)
+struct PlantSetup {
+  const i2c::ModelOps* ops;
+  I2cDims d;
+  double Le[I2C_SYM(I2C_MAX_NX)], Lz[I2C_SYM(I2C_MAX_NZ)];
+};
+// (buffers: also require the problem's device buffers -- the episode runs sweeps on them; the plant step alone reads none)
+int plant_setup(const I2cProblem* p, const double* sig_zeta, bool noise_x, bool noise_y, bool buffers, PlantSetup* s) {
+  const int rc = buffers ? check_problem(p) : check_problem_shape(p);
+  if (rc != I2C_OK) return rc;
+  s->ops = find_ops(p->model_id, p->dtype);
+  if (s->ops && p->model_params_b) s->ops = s->ops->per_traj;
+  if (!s->ops) return I2C_EINVAL;
+  s->ops->dims(&s->d);
+  if (noise_x && !chol_packed_host(p->sig_eta, s->d.nx, s->Le)) return I2C_EINVAL;
+  if (noise_y && (!sig_zeta || !chol_packed_host(sig_zeta, s->d.ny, s->Lz))) return I2C_EINVAL;
+  return I2C_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int i2c_plant_step(const I2cProblem* p, const double* sig_zeta, void* x, const void* u, const void* eps_x, const void* eps_y,
+                   void* y_out, void* x_obs, const void* z_ref, void* cost, void* stream) {
+  if (!x || !u || (eps_y && !y_out)) return I2C_EINVAL;
+  PlantSetup s;
+  const int rc = plant_setup(p, sig_zeta, eps_x != nullptr, eps_y != nullptr, false, &s);
+  if (rc != I2C_OK) return rc;
+  const i2c::PlantCall k{x,       u,     eps_x,   eps_y,   y_out,   nullptr, x_obs, nullptr, z_ref,
+                         cost,    nullptr, nullptr, nullptr, nullptr, eps_x ? s.Le : nullptr, eps_y ? s.Lz : nullptr};
+  return s.ops->plant_step(p, &k, stream);
+}
+
+int i2c_mpc_episode(const I2cProblem* p, const I2cMpcStep* m, I2cEpisode* ep, void* stream) {
+  if (!m || !m->post || !m->fwd || !m->term_stats || !m->cell_init || !m->status || !m->action || m->n_iter < 0) return I2C_EINVAL;
+  if (!ep || ep->n_steps < 0 || !ep->x_true || !ep->u || !ep->cost) return I2C_EINVAL;
+  if (ep->observe_state != 0 && ep->observe_state != 1) return I2C_EINVAL;
+  if (!ep->observe_state && !ep->y) return I2C_EINVAL;
+  if (ep->observe_state && (ep->eps_y || ep->y_hist)) return I2C_EINVAL;  // nothing is measured in that mode
+  if (p && p->alpha_cell && !m->alpha_init) return I2C_EINVAL;
+  if (ep->z_traj && (ep->n_z < 1 || !p || !p->z_per_cell || !p->z)) return I2C_EINVAL;
+  int rc = check_problem(p);
+  if (rc != I2C_OK) return rc;
+  const i2c::ModelOps* planner = find_ops(p->model_id, p->dtype);
+  if (planner && p->model_params_b) planner = planner->per_traj;
+  if (!planner) return I2C_EINVAL;
+  // the plant: the planner's problem with the plants' own parameters where they are given (check_problem refuses them on a model
+  // without parameters); only its model, noise, cost weights and parameters are read
+  I2cProblem plant = *p;
+  if (ep->plant_params_b) plant.model_params_b = ep->plant_params_b;
+  PlantSetup s;
+  rc = plant_setup(&plant, m->sig_zeta, ep->eps_x != nullptr, ep->eps_y != nullptr, true, &s);
+  if (rc != I2C_OK) return rc;
+  const size_t es = p->dtype == I2C_F32 ? 4 : 8, B = (size_t)p->B;
+  auto row = [&](const void* base, long k, int n) -> const char* {
+    return base ? (const char*)base + (size_t)k * (size_t)n * B * es : nullptr;
+  };
+  auto rowm = [&](void* base, long k, int n) -> void* { return const_cast<char*>(row(base, k, n)); };
+  const int nx = s.d.nx, nu = s.d.nu, nz = s.d.nz, ny = s.d.ny;
+  I2cProblem q = *p;  // the ring moves on this copy
+  I2cMpcStep st = *m;
+  st.y = ep->y;
+  st.u = ep->u;
+  ep->t0_out = q.t0;
+  ep->terminal_cell_out = q.terminal_cell;
+  for (int k = 0; k < ep->n_steps; ++k) {
+    st.do_filter = (!ep->observe_state && k >= 1) ? 1 : 0;
+    st.z_new = ep->z_traj ? row(ep->z_traj, (long)k + p->T < ep->n_z ? (long)k + p->T : ep->n_z - 1, nz) : nullptr;
+    rc = planner->mpc_step(&q, &st, stream);
+    if (rc != I2C_OK) return rc;
+    const i2c::PlantCall c{ep->x_true,
+                           m->action,
+                           row(ep->eps_x, k, nx),
+                           row(ep->eps_y, k, ny),
+                           ep->observe_state ? nullptr : ep->y,
+                           ep->u,
+                           ep->observe_state ? const_cast<void*>(p->x0) : nullptr,
+                           p->x0,
+                           ep->z_traj ? row(ep->z_traj, k < ep->n_z ? k : ep->n_z - 1, nz) : nullptr,
+                           ep->cost,
+                           rowm(ep->x_hist, k, nx),
+                           rowm(ep->u_hist, k, nu),
+                           rowm(ep->y_hist, k, ny),
+                           rowm(ep->mu_hist, k, nx),
+                           ep->eps_x ? s.Le : nullptr,
+                           ep->eps_y ? s.Lz : nullptr};
+    rc = s.ops->plant_step(&plant, &c, stream);
+    if (rc != I2C_OK) return rc;
+    q.t0 = (q.t0 + 1) % q.T;
+    if (q.terminal_cell >= 0) q.terminal_cell -= 1;
+    ep->t0_out = q.t0;  // (kept current step by step: after a launch error the caller still knows where the ring stands)
+    ep->terminal_cell_out = q.terminal_cell;
+  }
+  return I2C_OK;
 }
 
 }  // extern "C"

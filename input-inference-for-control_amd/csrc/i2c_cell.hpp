@@ -2144,6 +2144,121 @@ I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, 
 }
 
 // ------------------------------------------------------------------------------------------
+// One step of the PLANT under the action a control step just planned: the part of the closed MPC loop between two calls of
+// the policy (scripts/mpc_state_est/mpc_quad.py:643-660; env step :414-420, measurement :408-412), one lane per trajectory:
+//   history rows; cost[b] += (z - z_ref)^T QR (z - z_ref), z = observe(x, u);  x' = dynamics(x, u) + Le eps_x;
+//   y = measure(x') + Lz eps_y  (partially observed)   or   belief mean <- x'  (fully observed, mpc.py:95-111).
+// Le = chol(sig_eta) and Lz = chol(sig_zeta) are constant: factored once per call on the host (PlantNoise, kernel arguments).
+// The functors clip the action themselves, so the raw planned action is what is recorded and handed to the next filter step.
+// The plant's parameters are those of the problem the launcher was given (shared, or column b of model_params_b: PerTraj<M>).
+// ------------------------------------------------------------------------------------------
+template <class M, typename R> struct PlantNoise {
+  R Le[sym(M::NX)], Lz[sym(M::NY)];
+};
+template <typename R> struct PlantArgs {
+  R* x;            // [NX][B]  true state, in/out
+  const R* u;      // [NU][B]  the planned action (first NU rows of I2cMpcStep.action)
+  const R* eps_x;  // [NX][B] or null: process noise, standard normal
+  const R* eps_y;  // [NY][B] or null: measurement noise, standard normal
+  R* y_out;        // [NY][B] or null: the measurement the next filter step reads
+  R* u_out;        // [NU][B] or null: the applied action the next filter step reads
+  R* x_obs;        // [NX][B] or null: fully observed mode, the belief mean (I2cProblem.x0) takes x'
+  const R* mu;     // [NX][B] or null: the belief mean the plan started from, copied to mu_hist
+  const R* z_ref;  // [NZ][B] or null (the batch target c.zg): reference of this step's cost
+  R* cost;         // [B] or null: accumulated
+  R* x_hist;       // [NX][B] or null: x before the step
+  R* u_hist;       // [NU][B] or null
+  R* y_hist;       // [NY][B] or null: y after the step
+  R* mu_hist;      // [NX][B] or null
+};
+
+template <class M, typename R>
+I2C_HD inline void plant_step_body(const Consts<M, R>& c, const PlantNoise<M, R>& nz, const PlantArgs<R>& a, const int b) {
+  using C = Consts<M, R>;
+  constexpr int NX = C::NX, NU = C::NU, NZ = C::NZ, NY = M::NY, D = C::D, NA1 = M::NA > 0 ? M::NA : 1;
+  const long B = c.B;
+  R pb[C::NP1];
+  const R* prm = c.params;
+  if constexpr (is_per_traj<M>::value) prm = param_ptr<M::NP>(params_of(c, b), pb);
+  R xu[D], sn[NA1], cs[NA1], zt[NZ], xn[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) xu[i] = a.x[(long)i * B + b];
+#pragma unroll
+  for (int i = 0; i < NU; ++i) xu[NX + i] = a.u[(long)i * B + b];
+  if (a.x_hist) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) a.x_hist[(long)i * B + b] = xu[i];
+  }
+  if (a.u_hist) {
+#pragma unroll
+    for (int i = 0; i < NU; ++i) a.u_hist[(long)i * B + b] = xu[NX + i];
+  }
+  if (a.mu_hist) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) a.mu_hist[(long)i * B + b] = a.mu[(long)i * B + b];
+  }
+#pragma unroll
+  for (int q = 0; q < M::NA; ++q) r_sincos(xu[M::ang(q)], &sn[q], &cs[q]);
+  M::observe(prm, xu, sn, cs, zt);
+  M::dynamics(prm, xu, sn, cs, xn);
+  if (a.cost) {  // stage cost of (x, u) against this step's reference (mpc_quad.py:659-660)
+#pragma unroll
+    for (int k = 0; k < NZ; ++k) zt[k] -= a.z_ref ? a.z_ref[(long)k * B + b] : c.zg[k];
+    R q = R(0);
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+      R r = R(0);
+#pragma unroll
+      for (int j = 0; j < i; ++j) r += c.QR[tri(i, j)] * zt[j];
+      q += zt[i] * (c.QR[tri(i, i)] * zt[i] + R(2) * r);
+    }
+    a.cost[b] += q;
+  }
+  if (a.eps_x) {
+    R e[NX];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) e[j] = a.eps_x[(long)j * B + b];
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j) xn[i] += nz.Le[tri(i, j)] * e[j];
+  }
+#pragma unroll
+  for (int i = 0; i < NX; ++i) a.x[(long)i * B + b] = xn[i];
+  if (a.u_out) {
+#pragma unroll
+    for (int i = 0; i < NU; ++i) a.u_out[(long)i * B + b] = xu[NX + i];
+  }
+  if (a.x_obs) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) a.x_obs[(long)i * B + b] = xn[i];
+  }
+  if (a.y_out || a.y_hist) {
+    R y[NY];
+#pragma unroll
+    for (int q = 0; q < M::NA; ++q) r_sincos(xn[M::ang(q)], &sn[q], &cs[q]);
+    M::measure(prm, xn, sn, cs, y);
+    if (a.eps_y) {
+      R e[NY];
+#pragma unroll
+      for (int j = 0; j < NY; ++j) e[j] = a.eps_y[(long)j * B + b];
+#pragma unroll
+      for (int i = 0; i < NY; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) y[i] += nz.Lz[tri(i, j)] * e[j];
+    }
+    if (a.y_out) {
+#pragma unroll
+      for (int i = 0; i < NY; ++i) a.y_out[(long)i * B + b] = y[i];
+    }
+    if (a.y_hist) {
+#pragma unroll
+      for (int i = 0; i < NY; ++i) a.y_hist[(long)i * B + b] = y[i];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // Receding-horizon shift of the MPC loop (PartiallyObservedMpcPolicy.__call__, i2c/policy/mpc.py:171-181):
 //   u = cells[0].mu_u0_m;  cells.pop(0);  cells.append(deepcopy(cell_init)) with the next target.
 // The persistent per-cell buffers are a RING (Consts::t0): popping cell 0 and appending a cell is "advance t0 by one"

@@ -8,6 +8,19 @@
 
 namespace i2c {
 
+// One plant step of the closed MPC loop as the C-ABI unit hands it to a table (i2c_plant_step; every step of i2c_mpc_episode):
+// device buffers in the problem's arithmetic type, each optional one NULL to skip (PlantArgs, i2c_cell.hpp), and the two noise
+// factors, HOST packed lower Cholesky factors in double (NULL: that noise is off), computed once per call of the C entry point.
+struct PlantCall {
+  void* x;            // [nx][B] true state, in/out
+  const void* u;      // [nu][B] planned action
+  const void *eps_x, *eps_y;
+  void *y_out, *u_out, *x_obs;
+  const void *mu, *z_ref;
+  void *cost, *x_hist, *u_hist, *y_hist, *mu_hist;
+  const double *Le, *Lz;  // chol(sig_eta) [SYM(nx)], chol(sig_zeta) [SYM(ny)]
+};
+
 // (the C header names this table I2cModelOps, opaque: a model library hands it to i2c_register_model)
 struct ModelOps {
   int (*forward)(const I2cProblem*, const void* prior, void* fwd, void* prior_out, int32_t* status, void* stream);
@@ -35,6 +48,7 @@ struct ModelOps {
                          void* prop_hist, double tol, int tau, int n_iters, void* stats_hist, int use_expert, int overlap, int32_t* status,
                          void* stream);
   const ModelOps* per_traj;  // the same entry points with per-trajectory model parameters (I2cProblem.model_params_b); nullptr: NP = 0
+  int (*plant_step)(const I2cProblem*, const PlantCall*, void* stream);  // (ABI v9)
 };
 
 // defined by the translation units generated from i2c_model_tu.hip

@@ -186,6 +186,11 @@ template <class M, typename R> I2C_KERNEL(LANE_BLOCK) k_rollout(I2C_LANE_PARAMS 
   const long n = I2C_LANE_X(LANE_BLOCK);
   if (n < (long)a.n_rollouts * c.B) rollout_body<M, R>(c, a, (int)n);
 }
+template <class M, typename R>
+I2C_KERNEL(LANE_BLOCK) k_plant_step(I2C_LANE_PARAMS const Consts<M, R> c, const PlantNoise<M, R> nz, const PlantArgs<R> a) {
+  const long b = I2C_LANE_X(LANE_BLOCK);
+  if (b < c.B) plant_step_body<M, R>(c, nz, a, (int)b);
+}
 
 // Sum of the per-cell cost statistics over t: REDUCE_PARTS lanes per trajectory, fixed summation order; with `ms.alpha`
 // set (i2c_learn) the temperature M-step rides on it. The device form exchanges the partial sums through LDS; the host
@@ -1683,6 +1688,20 @@ template <class M, typename R, typename S = R> struct Impl {
     return launch(k_rollout<M, R>, (long)n_rollouts * p->B, 1, LANE_BLOCK, stream, c, a);
   }
 
+  // One plant step of the closed MPC loop (i2c_plant_step, and every step of i2c_mpc_episode): plant_step_body, one lane per
+  // trajectory for every model -- it is one dynamics, one observe and one measure evaluation, with nothing to share between lanes.
+  static int plant_step(const I2cProblem* p, const PlantCall* k, void* stream) {
+    if constexpr (MIXED) return I2C_ENOTSUP;
+    const C c = make_consts<M, R>(p, 0.0, 0);
+    PlantNoise<M, R> nz{};
+    for (int i = 0; i < sym(M::NX); ++i) nz.Le[i] = k->Le ? (R)k->Le[i] : R(0);
+    for (int i = 0; i < sym(M::NY); ++i) nz.Lz[i] = k->Lz ? (R)k->Lz[i] : R(0);
+    PlantArgs<R> a{(R*)k->x,           (const R*)k->u,     (const R*)k->eps_x, (const R*)k->eps_y, (R*)k->y_out,
+                   (R*)k->u_out,       (R*)k->x_obs,       (const R*)k->mu,    (const R*)k->z_ref, (R*)k->cost,
+                   (R*)k->x_hist,      (R*)k->u_hist,      (R*)k->y_hist,      (R*)k->mu_hist};
+    return launch(k_plant_step<M, R>, p->B, 1, LANE_BLOCK, stream, c, nz, a);
+  }
+
   static int propagate(const I2cProblem* p, const void* post, void* prop, void* prop_stats, int use_expert,
                        int32_t* status, void* stream) {
     if constexpr (MIXED) return I2C_ENOTSUP;
@@ -1735,7 +1754,8 @@ template <class M, typename R, typename S = R> const ModelOps* make_ops(const Mo
   using I = Impl<M, R, S>;
   static const ModelOps ops = {&I::forward, &I::backward,  &I::mstep,        &I::learn,           &I::ckf,
                                &I::rollout, &I::propagate, &I::riccati,   &I::mpc_step,        &fill_dims<M>,
-                               &workspace_elems<M>, &I::plan, &I::shift, &I::family_of, &I::learn_propagate, per_traj};
+                               &workspace_elems<M>, &I::plan, &I::shift, &I::family_of, &I::learn_propagate, per_traj,
+                               &I::plant_step};
   return &ops;
 }
 // ... the per-trajectory table itself: only models with parameters have one

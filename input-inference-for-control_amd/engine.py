@@ -756,7 +756,6 @@ class BatchedI2c:
         assert self.prior is self.post, "mpc_step() between a sweep and its update_priors()"
         st = _native.I2cMpcStep()
         st.do_filter = int(y is not None)
-        st.n_iter, st.tau = int(n_iter), int(self.tau)
         if y is not None:
             ny = self.dims.ny
             assert y.shape == (ny, self.B) and u.shape == (self.nu, self.B) and y.dtype == self.dtype
@@ -764,21 +763,158 @@ class BatchedI2c:
                 st.sig_zeta[i] = float(v)
             y, u = y.contiguous(), u.contiguous()
             st.y, st.u = y.data_ptr(), u.data_ptr()
+        self._fill_mpc_step(st, n_iter)
+        if z_new is not None:
+            z_new = z_new.contiguous()
+        st.z_new = None if z_new is None else z_new.data_ptr()
+        self._problem.expert_controller = int(bool(self.use_expert_controller))
+        rc = self.lib.i2c_mpc_step(C.byref(self._problem), C.byref(st), self._stream())
+        self._check(rc, "i2c_mpc_step")
+        self._advance_ring()
+        return self._mpc_action[: self.nu].T, self._mpc_action[self.nu:].T
+
+    # ------------------------------------------------------------------ the closed loop on the device
+    def _fill_mpc_step(self, st, n_iter):
+        """The fields of I2cMpcStep every control step of this engine shares (buffers, tau, the action row)."""
+        st.n_iter, st.tau = int(n_iter), int(self.tau)
         if getattr(self, "_mpc_action", None) is None:
             self._mpc_action = torch.empty(self.nu + sym_size(self.nu), self.B, dtype=self.dtype, device=self.device)
         st.post, st.fwd = self.post.data_ptr(), self.fwd.data_ptr()
         opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         st.xm, st.zpost, st.cell_stats, st.term_stats = opt(self.xm), opt(self.zpost), opt(self.cell_stats), self.term_stats.data_ptr()
         st.cell_init, st.alpha_init = self.cell_init.data_ptr(), opt(self.alpha_init)
-        if z_new is not None:
-            z_new = z_new.contiguous()
-        st.z_new = opt(z_new)
         st.action, st.status = self._mpc_action.data_ptr(), self.status.data_ptr()
+
+    def _sig_zeta(self, sig_zeta, needed):
+        """The measurement noise (ny, ny): the argument, else sys.sig_zeta; packed (ctypes array) or None."""
+        if sig_zeta is None:
+            sig_zeta = getattr(self.sys, "sig_zeta", None)
+        if sig_zeta is None:
+            if needed:
+                raise ValueError("sig_zeta (measurement noise) is needed: pass it or set sys.sig_zeta")
+            return None
+        ny = self.dims.ny
+        sig_zeta = np.asarray(sig_zeta, np.float64)
+        assert sig_zeta.shape == (ny, ny), f"sig_zeta must be ({ny}, {ny}), got {sig_zeta.shape}"
+        return pack_sym_np(sig_zeta).reshape(-1)
+
+    def _state_rows(self, a, n):
+        """(B, n) / (n,) array or tensor -> a new contiguous [n][B] device tensor."""
+        if torch.is_tensor(a):
+            a = a.detach().to(self.device, self.dtype).reshape(-1, n)
+            return a.expand(self.B, n).T.contiguous()
+        a = np.broadcast_to(np.asarray(a, np.float64).reshape(-1, n), (self.B, n))
+        return torch.as_tensor(np.array(a.T, order="C"), dtype=self.dtype, device=self.device)
+
+    def plant_step(self, x, u, sig_zeta=None, eps_x=None, eps_y=None, y_out=None, observe_state=False, z_ref=None, cost=None,
+                   plant_params=None):
+        """One step of B noisy plants on the device (i2c_plant_step): the host code between two control steps of a closed loop
+        (mpc_quad.py:643-660). x: [nx][B] tensor, the true states, UPDATED IN PLACE; u: [nu][B] tensor, the action (e.g. the
+        transposed first result of mpc_step). eps_x [nx][B] / eps_y [ny][B]: standard-normal samples or None (no noise of that
+        kind). cost: optional (B,) tensor the stage cost (z - z_ref)^T QR (z - z_ref) is ADDED to; z_ref [nz][B] or None (sys.zg);
+        z = observe(x, u) of the action as given (the dynamics clip it themselves, the cost does not: clip u first for that).
+        observe_state=True: the belief mean x0 takes the new state and nothing is measured (MpcPolicy.__call__(i, x)); otherwise
+        returns the measurement y [ny][B] (written into y_out when given) for the next mpc_step(y=..., u=...).
+        plant_params: (B, NP) parameters of the plants when they differ from the planner's model."""
+        nx, nu, ny, B = self.nx, self.nu, self.dims.ny, self.B
+        assert x.shape == (nx, B) and x.is_contiguous() and x.dtype == self.dtype and x.device.type == self.device.type
+        assert u.shape == (nu, B) and u.dtype == self.dtype
+        u = u.contiguous()
+        chk = lambda t, n: None if t is None else t.to(self.dtype).reshape(n, B).contiguous()  # noqa: E731
+        eps_x, eps_y, z_ref = chk(eps_x, nx), chk(eps_y, ny), chk(z_ref, self.nz)
+        if observe_state:
+            assert eps_y is None and y_out is None, "nothing is measured in the fully observed mode"
+        elif y_out is None:
+            y_out = torch.empty(ny, B, dtype=self.dtype, device=self.device)
+        if y_out is not None:
+            assert y_out.shape == (ny, B) and y_out.is_contiguous() and y_out.dtype == self.dtype
+        if cost is not None:
+            assert cost.shape == (B,) and cost.is_contiguous() and cost.dtype == self.dtype
+        zeta = self._sig_zeta(sig_zeta, eps_y is not None)
+        zeta_c = None if zeta is None else (C.c_double * len(zeta))(*zeta)
+        problem, plant = self._problem, None
+        if plant_params is not None:
+            plant = self._params_to_device(plant_params)
+            problem = self._make_problem()
+            problem.model_params_b = plant.data_ptr()
+        rc = self.lib.i2c_plant_step(C.byref(problem), zeta_c, self._ptr(x), self._ptr(u), self._ptr(eps_x), self._ptr(eps_y),
+                                     self._ptr(y_out), self._ptr(self.x0) if observe_state else None, self._ptr(z_ref),
+                                     self._ptr(cost), self._stream())
+        self._check(rc, "i2c_plant_step")
+        return y_out
+
+    def run_closed_loop(self, n_steps, n_iter, sig_zeta=None, x_true=None, process_noise=True, measurement_noise=True,
+                        generator=None, plant_params=None, z_traj=None, observe_state=False, keep=("x", "u"), eps_x=None, eps_y=None):
+        """A closed-loop MPC episode of n_steps control steps in ONE library call (i2c_mpc_episode), no host round trip: per step
+        mpc_step(n_iter) -- with the cubature Kalman filter on the last measurement and action from the second step on -- then
+        the noisy plants (plant_step). The loop of scripts/mpc_state_est/mpc_quad.py:643-660 for B systems at once.
+          x_true            (B, nx) / (nx,) true initial states; None: the belief mean x0
+          process_noise / measurement_noise   draw eps_x (N, nx, B) / eps_y (N, ny, B) with torch.randn(generator=generator) on the
+                            engine's device (a seed reproduces an episode); eps_x / eps_y: use these samples instead
+          sig_zeta          (ny, ny) measurement noise of the filter and the plant; None: sys.sig_zeta
+          plant_params      (B, NP): the plants' parameters where they differ from the planner's model
+          z_traj            (n_z, nz) or (B, n_z, nz) reference from THIS step on: row min(k, n_z - 1) prices step k, row
+                            min(k + T, n_z - 1) is the target of the cell appended at step k (mpc.py:177-181). An engine without
+                            per-cell targets gets rows 0 .. T-1 as its horizon's first; one that has them keeps its own.
+                            None: the cost reference is sys.zg and an appended cell repeats the last target
+          observe_state     fully observed loop (MpcPolicy.__call__(i, x)): the belief mean is the plant's state, no filter
+          keep              which histories to return, of "x", "u", "y", "mu"
+        Returns a dict of device tensors: x (B, N, nx) states before each step, u (B, N, nu), y (B, N, ny) measurements after
+        each step, mu (B, N, nx) belief means the plans started from (as kept); cost (B,) summed tracking cost; x_true (B, nx)
+        final states; eps_x / eps_y as used. The ring (t0, terminal_cell) is advanced as n_steps calls of mpc_step would.
+        u and the cost are of the action AS PLANNED: the models' dynamics clip it to the actuator limits themselves, observe(x, u)
+        does not, where the reference's loop clips first and records / prices the clipped action (mpc_quad.py:645-647, 659). They
+        agree whenever the plan respects the limits.
+        A trajectory that fails numerically is flagged in status (failures()); its rows go non-finite, the others are untouched."""
+        assert self.prior is self.post, "run_closed_loop() between a sweep and its update_priors()"
+        N, B, T, dev, dt = int(n_steps), self.B, self.H, self.device, self.dtype
+        nx, nu, nz, ny = self.nx, self.nu, self.nz, self.dims.ny
+        unknown = set(keep) - {"x", "u", "y", "mu"}
+        if unknown or (observe_state and "y" in keep):
+            raise ValueError(f"keep={keep!r}: any of 'x', 'u', 'y', 'mu' ('y' only when the state is not observed)")
+        rnd = lambda *s: torch.randn(*s, dtype=dt, device=dev, generator=generator)  # noqa: E731
+        given = lambda t, shape: torch.as_tensor(t, dtype=dt, device=dev).reshape(shape).contiguous()  # noqa: E731
+        eps_x = given(eps_x, (N, nx, B)) if eps_x is not None else (rnd(N, nx, B) if process_noise else None)
+        if observe_state:
+            eps_y = None
+        else:
+            eps_y = given(eps_y, (N, ny, B)) if eps_y is not None else (rnd(N, ny, B) if measurement_noise else None)
+        zeta = self._sig_zeta(sig_zeta, not observe_state)
+        x = self.x0.clone() if x_true is None else self._state_rows(x_true, nx)
+        zt = None
+        if z_traj is not None:
+            z = np.asarray(z_traj, np.float64)
+            z = np.broadcast_to(z if z.ndim == 3 else z[None], (B, z.shape[-2], nz))
+            if self.z is None:
+                self.set_targets(z[:, np.minimum(np.arange(T), z.shape[1] - 1)])
+            zt = torch.as_tensor(np.array(np.transpose(z, (1, 2, 0)), order="C"), dtype=dt, device=dev)
+        st = _native.I2cMpcStep()
+        self._fill_mpc_step(st, n_iter)
+        if zeta is not None:
+            for i, v in enumerate(zeta):
+                st.sig_zeta[i] = float(v)
+        if getattr(self, "_loop_yu", None) is None:
+            self._loop_yu = torch.zeros(ny + nu, B, dtype=dt, device=dev)
+        hist = {k: torch.empty(N, n, B, dtype=dt, device=dev) if k in keep else None
+                for k, n in (("x", nx), ("u", nu), ("y", ny), ("mu", nx))}
+        cost = torch.zeros(B, dtype=dt, device=dev)
+        plant = None if plant_params is None else self._params_to_device(plant_params)
+        ep = _native.I2cEpisode()
+        ep.n_steps, ep.observe_state, ep.n_z = N, int(bool(observe_state)), 0 if zt is None else int(zt.shape[0])
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        ep.x_true, ep.eps_x, ep.eps_y, ep.plant_params_b, ep.z_traj = x.data_ptr(), opt(eps_x), opt(eps_y), opt(plant), opt(zt)
+        ep.y, ep.u = self._loop_yu[:ny].data_ptr(), self._loop_yu[ny:].data_ptr()
+        ep.x_hist, ep.u_hist, ep.y_hist, ep.mu_hist = opt(hist["x"]), opt(hist["u"]), opt(hist["y"]), opt(hist["mu"])
+        ep.cost = cost.data_ptr()
+        ep.t0_out, ep.terminal_cell_out = int(self.t0), int(self.terminal_cell)
         self._problem.expert_controller = int(bool(self.use_expert_controller))
-        rc = self.lib.i2c_mpc_step(C.byref(self._problem), C.byref(st), self._stream())
-        self._check(rc, "i2c_mpc_step")
-        self._advance_ring()
-        return self._mpc_action[: self.nu].T, self._mpc_action[self.nu:].T
+        rc = self.lib.i2c_mpc_episode(C.byref(self._problem), C.byref(st), C.byref(ep), self._stream())
+        self.t0, self.terminal_cell = int(ep.t0_out), int(ep.terminal_cell_out)  # where the call reports the ring, also after an error part-way
+        self._problem.t0, self._problem.terminal_cell = self.t0, self.terminal_cell
+        self._check(rc, "i2c_mpc_episode")
+        out = {k: v.permute(2, 0, 1) for k, v in hist.items() if v is not None}
+        out.update(cost=cost, x_true=x.T, eps_x=eps_x, eps_y=eps_y)
+        return out
 
     def set_targets(self, z_traj):
         """Per-cell targets (mpc.py:29-31): z_traj (T, nz) or (B, T, nz)."""
