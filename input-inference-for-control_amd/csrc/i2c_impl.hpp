@@ -7,6 +7,11 @@
 //                                                                 looped on the CPU so that kernel
 //                                                                 numerics can be checked against the
 //                                                                 oracle on a box without a GPU)
+//
+// Layout: the launch layer of the one-lane kernels (launch(), I2C_KERNEL) and those kernels; the launch layer of the multi-lane
+// kernels (host simulation: sim_teams(); device: I2C_QUAD_SETUP / launch_quad(), the XCD placement) and the group, wave and quad
+// kernels, each with its launcher; the problem constants, the chunk workspace and the per-model batch sizes; Impl<M, R, S>: which
+// family and schedule serve a call, and the entry points.
 #pragma once
 #include "i2c_entry.hpp"
 #include "i2c_cell.hpp"
@@ -36,6 +41,8 @@ constexpr int LANE_BLOCK = I2C_LANE_BLOCK;
 constexpr int CELL_BLOCK = 256;
 
 // ---- the ONE place that knows how a per-lane body runs ---------------------------------------------------------------
+// (one lane per trajectory; the bodies that run as a TEAM of lanes -- group, wave and quad kernels -- have theirs further down:
+// "the ONE place that knows how a multi-lane body runs")
 // Device: a HIP kernel, lane index from the block / thread ids, started by launch() through hipLaunchKernelGGL.
 // Host simulation (tests only): the same function with the lane indices as leading arguments, looped by launch().
 // A kernel is written once:   template <...> I2C_KERNEL(BLOCK) k_name(I2C_LANE_PARAMS const C c, const A a) {
@@ -252,6 +259,63 @@ static int launch_reduce(const Consts<M, R>& c, const CA& a, const MstepArgs<R>&
 }
 #endif
 
+// ---- the ONE place that knows how a multi-lane body runs -----------------------------------------------------------------------
+// The group, wave and quad kernels run a body as a TEAM of lanes (G, 64, 64) that share an LDS region and exchange values across lanes.
+// Device: the set-up of a team lives in one place per family -- k_group, k_wave, and for the seven quad kernels I2C_QUAD_SETUP (constants
+// into LDS, the lane's four-trajectory slot, the wave-uniform exit, the Quad<R>) with launch_quad() (grid formula, error tail).
+// Host simulation (tests only): sim_teams() is the only function that starts threads; a launcher passes it the team size, the LDS size
+// and its body, sim_quad() adds the decoding of a quad lane. Each launch_*() below is written once, with the two forms side by side.
+// Shared by both: the unit-rule predicate and the GENERAL x LEANQ variant choice of the quad launchers.
+
+// cubature weights with lam = 0: unit weights, no weight on the centre (every shipped config) -- of one rule, or of both rules of a problem
+template <typename R> static bool unit_rule(const Rule<R>& r) { return r.unit && r.w0 == R(0); }
+template <class M, typename R> static bool unit_rule(const Consts<M, R>& c) { return unit_rule(c.rule_xu) && unit_rule(c.rule_x); }
+
+#ifdef I2C_HOST_SIM
+// body(i, y, l, sh, &bar, xch) for every team i < n_teams, grid row y < n_rows and lane l < team: the lanes of a team are threads that share
+// a barrier (waited on wherever the device code has its LDS fence or a cross-lane instruction), a zeroed LDS region of `lds` elements and
+// the 128 exchange slots of the emulated cross-lane instructions. rows_on_team = false: every grid row is a team of its own (one CELL per
+// row: the wave two-pass schedule). true: a team walks its rows one after the other on the same threads (one CHUNK per row: the simulated
+// wavefront of a quad group walks its chunks in turn -- 64 threads per group, not 64 per group and chunk).
+template <typename R, class Body>
+static void sim_teams(const int team, const long n_teams, const int n_rows, const bool rows_on_team, const size_t lds, const Body& body) {
+  for (int y0 = 0; y0 < (rows_on_team ? 1 : n_rows); ++y0)
+    for (long i = 0; i < n_teams; ++i) {
+      std::vector<R> sh(lds, R(0)), xch(128, R(0));
+      HostBarrier bar(team);
+      std::vector<std::thread> lanes;
+      for (int l = 0; l < team; ++l)
+        lanes.emplace_back([&, l] {
+          for (int y = y0; y < (rows_on_team ? n_rows : y0 + 1); ++y) body(i, y, l, lds ? sh.data() : (R*)nullptr, &bar, xch.data());
+        });
+      for (auto& th : lanes) th.join();
+    }
+}
+#else
+// The batch constants are unpacked into LDS with per-lane indices, read straight from the kernel-argument segment: `c` is the first
+// kernel parameter (offset 0), `zeta` -- where a kernel has it -- follows it at its natural alignment.
+template <class M, typename R> __device__ __forceinline__ const Consts<M, R>* kernarg_consts() {
+  return (const Consts<M, R>*)__builtin_amdgcn_kernarg_segment_ptr();
+}
+template <class M, typename R> __device__ __forceinline__ const R* kernarg_zeta() {
+  constexpr size_t zoff = (sizeof(Consts<M, R>) + alignof(ZetaArg<M, R>) - 1) / alignof(ZetaArg<M, R>) * alignof(ZetaArg<M, R>);
+  return ((const ZetaArg<M, R>*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + zoff))->v;
+}
+// XCD placement: first trajectory of workgroup i, and the grid that covers B trajectories with it (one wave of k_wave = one trajectory,
+// four waves per workgroup; one single-wave workgroup of k_quad_forward = four trajectories).
+// k_wave: a wave reads ONE 8-byte element of every [B]-contiguous row: the 16 trajectories that share a 128-byte line of each row
+// are mapped onto four workgroups of the SAME XCD (workgroups are dealt round-robin over the 8 XCDs, so blocks i and i + 8
+// share an L2): every line is then fetched from HBM once per XCD instead of once per wave.
+// k_quad_forward with single-wave workgroups: a wave reads four consecutive trajectories (32 bytes) of every [B]-contiguous row: the
+// four waves that share a 128-byte line of each row are mapped onto workgroups of the SAME XCD in the same way.
+// Placement is a speed heuristic only -- any mapping computes the same result.
+__device__ __forceinline__ long xcd_first_traj(const unsigned i) {
+  const unsigned x = i & 7u, r = (i >> 3) & 3u, g = i >> 5;
+  return 16L * (g * 8u + x) + 4 * r;
+}
+static unsigned xcd_blocks(const long B) { return (unsigned)((B + 127) / 128) * 32u; }
+#endif
+
 // ---- group kernels (i2c_group.hpp): G lanes per trajectory, 64 / G trajectories per wavefront ------------------------
 // KIND selects the sweep; the bodies share their argument plumbing. Device: one wave per workgroup, the batch constants
 // and every group's exchange region in LDS. Host simulation: the G lanes of a group are G threads.
@@ -264,34 +328,12 @@ I2C_FN void group_body(const Consts<M, R>& c, const KC& kc, const A& a, const in
   if constexpr (KIND == GK_PROPAGATE) propagate_group_body<M, R, G, FULLW>(c, kc, a, b, g);
   if constexpr (KIND == GK_CKF) ckf_group_body<M, R, G>(c, kc, a, b, g);
 }
-#ifdef I2C_HOST_SIM
-template <int KIND, class M, typename R, int G, bool FULLW, class A>
-static int launch_group_w(const Consts<M, R>& c, const ZetaArg<M, R>* zeta, const A& a, void*) {
-  GConst<M, R> kc;
-  gconst_fill<M, R>(kc, &c, zeta ? zeta->v : (const R*)nullptr, 0, 1);
-  for (int b = 0; b < c.B; ++b) {
-    std::vector<R> sh((size_t)Grp<R, G>::SIZE, R(0));
-    HostBarrier bar(G);
-    std::vector<std::thread> lanes;
-    for (int r = 0; r < G; ++r)
-      lanes.emplace_back([&, r] { group_body<KIND, M, R, G, FULLW>(c, kc, a, b, Grp<R, G>{r, sh.data(), &bar}); });
-    for (auto& th : lanes) th.join();
-  }
-  return I2C_OK;
-}
-#else
+#ifndef I2C_HOST_SIM
 template <int KIND, class M, typename R, int G, bool FULLW, class A>
 __global__ __launch_bounds__(SWEEP_BLOCK) void k_group(const Consts<M, R> c, const ZetaArg<M, R> zeta, const int has_zeta, const A a) {
   __shared__ GConst<M, R> kc;
   __shared__ R sh[(SWEEP_BLOCK / G) * Grp<R, G>::SIZE];
-  {
-    // The batch constants are unpacked into LDS with per-lane indices, read straight from the kernel-argument segment:
-    // `c` is the first kernel parameter (offset 0), `zeta` follows it at its natural alignment.
-    const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t zoff = (sizeof(Consts<M, R>) + alignof(ZetaArg<M, R>) - 1) / alignof(ZetaArg<M, R>) * alignof(ZetaArg<M, R>);
-    gconst_fill<M, R>(kc, (const Consts<M, R>*)ka, has_zeta ? ((const ZetaArg<M, R>*)(ka + zoff))->v : (const R*)nullptr,
-                      (int)threadIdx.x, SWEEP_BLOCK);
-  }
+  gconst_fill<M, R>(kc, kernarg_consts<M, R>(), has_zeta ? kernarg_zeta<M, R>() : (const R*)nullptr, (int)threadIdx.x, SWEEP_BLOCK);
   __syncthreads();
   const long lane = (long)blockIdx.x * SWEEP_BLOCK + threadIdx.x;
   const long b = lane / G;
@@ -299,16 +341,25 @@ __global__ __launch_bounds__(SWEEP_BLOCK) void k_group(const Consts<M, R> c, con
   const Grp<R, G> g{(int)(threadIdx.x % G), (lds_ptr<R>)(sh + (threadIdx.x / G) * Grp<R, G>::SIZE)};
   group_body<KIND, M, R, G, FULLW>(c, kc, a, (int)b, g);
 }
+#endif
 template <int KIND, class M, typename R, int G, bool FULLW, class A>
 static int launch_group_w(const Consts<M, R>& c, const ZetaArg<M, R>* zeta, const A& a, void* stream) {
+#ifdef I2C_HOST_SIM
+  GConst<M, R> kc;
+  gconst_fill<M, R>(kc, &c, zeta ? zeta->v : (const R*)nullptr, 0, 1);
+  sim_teams<R>(G, c.B, 1, false, Grp<R, G>::SIZE, [&](const long b, int, const int r, R* sh, HostBarrier* bar, R*) {
+    group_body<KIND, M, R, G, FULLW>(c, kc, a, (int)b, Grp<R, G>{r, sh, bar});
+  });
+  return I2C_OK;
+#else
   ZetaArg<M, R> z{};
   if (zeta) z = *zeta;
   const long lanes = (long)c.B * G;
   hipLaunchKernelGGL((k_group<KIND, M, R, G, FULLW, A>), dim3((unsigned)((lanes + SWEEP_BLOCK - 1) / SWEEP_BLOCK)), dim3(SWEEP_BLOCK), 0,
                      (hipStream_t)stream, c, z, zeta ? 1 : 0, a);
   return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
-}
 #endif
+}
 
 // ---- wave kernels (i2c_wave.hpp): one wavefront per trajectory, four per workgroup ----------------------------------------------
 enum { WK_FORWARD = 0, WK_BACKWARD = 1, WK_SCAN = 2, WK_CELL = 3, WK_FORWARD_PL = 4 };  // _PL: pivot blocks through LDS
@@ -321,48 +372,35 @@ I2C_FN void wave_body(const Consts<M, R>& c, const KC& kc, const A& a, const int
   if constexpr (KIND == WK_SCAN) backward_wave_scan_body<M, R, S>(c, kc, a, b, w);
   if constexpr (KIND == WK_CELL) backward_wave_cell_body<M, R, S>(c, kc, a, t, b, w);  // one wave per (t, b)
 }
-#ifdef I2C_HOST_SIM
-template <int KIND, class M, typename R, typename S, bool LIN, class A>
-static int launch_wave_v(const Consts<M, R>& c, const A& a, void*) {
-  WConst<M, R> kc;
-  wconst_fill<M, R>(kc, &c, 0, 1);
-  for (int t = 0; t < (KIND == WK_CELL ? c.T : 1); ++t)
-    for (int b = 0; b < c.B; ++b) {
-      std::vector<R> sh((size_t)WaveLds::SIZE, R(0)), xch(128, R(0));
-      HostBarrier bar(64);
-      std::vector<std::thread> lanes;
-      for (int l = 0; l < 64; ++l)
-        lanes.emplace_back([&, l, t, b] { wave_body<KIND, M, R, S, LIN>(c, kc, a, t, b, Wave<R>{l, l >> 4, l & 15, sh.data(), &bar, xch.data()}); });
-      for (auto& th : lanes) th.join();
-    }
-  return I2C_OK;
-}
-#else
+#ifndef I2C_HOST_SIM
 template <int KIND, class M, typename R, typename S, bool LIN, class A>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 2) void k_wave(const Consts<M, R> c, const A a) {
   __shared__ WConst<M, R> kc;
   __shared__ R sh[WAVES_PER_BLOCK * WaveLds::SIZE];
-  wconst_fill<M, R>(kc, (const Consts<M, R>*)__builtin_amdgcn_kernarg_segment_ptr(), (int)threadIdx.x, 64 * WAVES_PER_BLOCK);
+  wconst_fill<M, R>(kc, kernarg_consts<M, R>(), (int)threadIdx.x, 64 * WAVES_PER_BLOCK);
   __syncthreads();
-  // A wave reads ONE 8-byte element of every [B]-contiguous row: the 16 trajectories that share a 128-byte line of each row
-  // are mapped onto four workgroups of the SAME XCD (workgroups are dealt round-robin over the 8 XCDs, so blocks i and i + 8
-  // share an L2): every line is then fetched from HBM once per XCD instead of once per wave. Placement is a speed heuristic
-  // only -- any mapping computes the same result.
-  const unsigned i = blockIdx.x, x = i & 7u, r = (i >> 3) & 3u, g = i >> 5;
-  const long b = 16L * (g * 8u + x) + 4 * r + (threadIdx.x >> 6);
+  const long b = xcd_first_traj(blockIdx.x) + (threadIdx.x >> 6);
   if (b >= c.B) return;
   const int l = (int)(threadIdx.x & 63u);
   const Wave<R> w{l, l >> 4, l & 15, (lds_ptr<R>)(sh + (threadIdx.x >> 6) * WaveLds::SIZE)};
   wave_body<KIND, M, R, S, LIN>(c, kc, a, (int)blockIdx.y, (int)b, w);
 }
+#endif
 template <int KIND, class M, typename R, typename S, bool LIN, class A>
 static int launch_wave_v(const Consts<M, R>& c, const A& a, void* stream) {
-  const unsigned blocks = (unsigned)(((long)c.B + 127) / 128) * 32u;
-  hipLaunchKernelGGL((k_wave<KIND, M, R, S, LIN, A>), dim3(blocks, KIND == WK_CELL ? (unsigned)c.T : 1u), dim3(64 * WAVES_PER_BLOCK), 0,
-                     (hipStream_t)stream, c, a);
+  const int n_rows = KIND == WK_CELL ? c.T : 1;
+#ifdef I2C_HOST_SIM
+  WConst<M, R> kc;
+  wconst_fill<M, R>(kc, &c, 0, 1);
+  sim_teams<R>(64, c.B, n_rows, false, WaveLds::SIZE, [&](const long b, const int t, const int l, R* sh, HostBarrier* bar, R* xch) {
+    wave_body<KIND, M, R, S, LIN>(c, kc, a, t, (int)b, Wave<R>{l, l >> 4, l & 15, sh, bar, xch});
+  });
+  return I2C_OK;
+#else
+  hipLaunchKernelGGL((k_wave<KIND, M, R, S, LIN, A>), dim3(xcd_blocks(c.B), (unsigned)n_rows), dim3(64 * WAVES_PER_BLOCK), 0, (hipStream_t)stream, c, a);
   return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
-}
 #endif
+}
 
 // ---- quad kernels (i2c_quad.hpp): four trajectories per wavefront, four wavefronts per workgroup ------------------------------
 // Workgroup of the quad kernels: FOUR wavefronts for every model (round 5; d <= 8 had one). With single-wave workgroups the
@@ -376,78 +414,125 @@ static int launch_wave_v(const Consts<M, R>& c, const A& a, void* stream) {
 #define I2C_QUAD_WPB 4
 #endif
 template <class M> constexpr int quad_waves_per_block() { return QG<M>::WIDE ? 4 : I2C_QUAD_WPB; }
+constexpr int QB_WAVES_PER_BLOCK = 4;  // ... and of the backward sweep and the chunk passes
+// the batch constants of a quad kernel, by the type of its LDS copy (zeta: the filter step's alone; NoConst: the compose pass has none)
+struct NoConst {};
+template <class M, typename R> I2C_FN void quad_const_fill(NoConst&, const Consts<M, R>*, const R*, const int, const int) {}
+template <class M, typename R> I2C_FN void quad_const_fill(QConst<M, R>& k, const Consts<M, R>* c, const R*, const int tid, const int n) { qconst_fill<M, R>(k, c, tid, n); }
+template <class M, typename R> I2C_FN void quad_const_fill(QBConst<M, R>& k, const Consts<M, R>* c, const R*, const int tid, const int n) { qbconst_fill<M, R>(k, c, tid, n); }
+template <class M, typename R> I2C_FN void quad_const_fill(QPConst<M, R>& k, const Consts<M, R>* c, const R*, const int tid, const int n) { qpconst_fill<M, R>(k, c, tid, n); }
+template <class M, typename R> I2C_FN void quad_const_fill(QKConst<M, R>& k, const Consts<M, R>* c, const R* zeta, const int tid, const int n) { qkconst_fill<M, R>(k, c, zeta, tid, n); }
 #ifdef I2C_HOST_SIM
-template <class M, typename R, typename S, bool GENERAL, class A>
-static int launch_quad_forward_g(const Consts<M, R>& c, const A& a, void*) {
-  QConst<M, R> kc;
-  qconst_fill<M, R>(kc, &c, 0, 1);
-  for (int b0 = 0; b0 < c.B; b0 += 4) {
-    std::vector<R> sh((size_t)4 * QG<M>::SIZE, R(0)), xch(128, R(0));
-    HostBarrier bar(64);
-    std::vector<std::thread> lanes;
-    for (int l = 0; l < 64; ++l)
-      lanes.emplace_back([&, l, b0] {
-        const int g = (l >> 2) & 3, b = b0 + g;
-        const bool live = b < c.B;
-        forward_quad_body<M, R, S, GENERAL>(c, kc, a, live ? b : c.B - 1, live, Quad<R>{l, l >> 4, g, l & 3, sh.data() + g * QG<M>::SIZE, &bar, xch.data()});
-      });
-    for (auto& th : lanes) th.join();
-  }
+// a simulated quad wavefront: lane l serves slot g = (l >> 2) & 3 of its four trajectories with `lsz` LDS elements each; the slots behind the
+// batch's end run on its last trajectory with live = false. body(kc, b, live, q, chunk); n_chunks = 0: a kernel without a chunk row
+template <class KC, class M, typename R, class Body>
+static int sim_quad(const Consts<M, R>& c, const R* zeta, const int lsz, const int n_chunks, const Body& body) {
+  KC kc;
+  quad_const_fill<M, R>(kc, &c, zeta, 0, 1);
+  sim_teams<R>(64, (c.B + 3) / 4, n_chunks ? n_chunks : 1, true, (size_t)4 * lsz, [&](const long i, const int ch, const int l, R* sh, HostBarrier* bar, R* xch) {
+    const int g = (l >> 2) & 3, b = 4 * (int)i + g;
+    const bool live = b < c.B;
+    body(kc, live ? b : c.B - 1, live, Quad<R>{l, l >> 4, g, l & 3, sh ? sh + g * lsz : sh, bar, xch}, ch);
+  });
   return I2C_OK;
 }
 #else
+// THE set-up of a quad kernel, from the constants into LDS to the finished Quad<R>: a macro in the style of I2C_KERNEL -- the statements
+// are the kernel's own, so `kc` and `sh` are its __shared__ objects and `l`, `wv`, `g`, `b`, `live`, `q` its constants. A kernel reads
+//   { I2C_QUAD_SETUP(waves per workgroup, LDS elements per trajectory, FORWARD, type of the constants); its_body(c, kc, a, b, live, q); }
+// `kc` is filled from the kernel-argument segment by the whole workgroup; lane l serves slot g = (l >> 2) & 3 of its wave's four
+// trajectories; a wave without a trajectory leaves the kernel (wave-uniform); the slots behind the batch's end run on its last
+// trajectory with live = false. FORWARD: k_quad_forward, which alone has the single-wave workgroup experiment (-DI2C_QUAD_WPB=1: XCD
+// placement) and the two diagnostic builds. I2C_QUAD_LANE is the part without constants and LDS (the compose pass).
+template <int WPB, bool FORWARD> __device__ __forceinline__ long quad_first_traj(const int wv) {
+  if constexpr (FORWARD && WPB == 1) return xcd_first_traj(blockIdx.x);
+  // the waves of a workgroup take consecutive groups of four trajectories: one 128-byte line of a [B]-contiguous row (the d = 16
+  // backward sweep has trajectory-major buffers: nothing is shared between its waves)
+  else return 4L * ((long)blockIdx.x * WPB + wv);
+}
+#ifdef I2C_QUAD_PLACEMENT  // (diagnostic build, never shipped: where the dispatcher put this wave -- tools/placement_summary.py)
+#define I2C_QUAD_PLACEMENT_PRINT(FORWARD)                                                                                      \
+  if (FORWARD && l == 0)                                                                                                       \
+    printf("placement %u %d %u %u\n", blockIdx.x, b0 < c.B ? 1 : 0, (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4),       \
+           (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20));
+#else
+#define I2C_QUAD_PLACEMENT_PRINT(FORWARD)
+#endif
+#ifdef I2C_QF_NOSTORE  // (experiment, never shipped: the sweep without its stores -- how much of it is the store path)
+constexpr bool QF_NOSTORE = true;
+#else
+constexpr bool QF_NOSTORE = false;
+#endif
+#define I2C_QUAD_LANE(WPB_, LDS, FORWARD)                                                                  \
+  const int l = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6), g = (l >> 2) & 3;                  \
+  const long b0 = quad_first_traj<WPB_, FORWARD>(wv);                                                      \
+  I2C_QUAD_PLACEMENT_PRINT(FORWARD)                                                                        \
+  if (b0 >= c.B) return; /* (wave-uniform: no trajectory in this wave) */                                  \
+  const bool live = (FORWARD && QF_NOSTORE) ? false : b0 + g < c.B;                                        \
+  const int b = (int)(b0 + g < c.B ? b0 + g : c.B - 1);                                                    \
+  const Quad<R> q{l, l >> 4, g, l & 3, LDS};
+#define I2C_QUAD_SETUP(WPB_, LSZ_, FORWARD, ...)                                                           \
+  constexpr int WPB = WPB_, LSZ = LSZ_;                                                                    \
+  __shared__ __VA_ARGS__ kc;                                                                               \
+  __shared__ R sh[WPB * 4 * LSZ];                                                                          \
+  quad_const_fill<M, R>(kc, kernarg_consts<M, R>(),                                                        \
+                        std::is_same<__VA_ARGS__, QKConst<M, R>>::value ? kernarg_zeta<M, R>() : (const R*)nullptr, /* (its 2nd parameter) */ \
+                        (int)threadIdx.x, 64 * WPB);                                                       \
+  __syncthreads();                                                                                         \
+  I2C_QUAD_LANE(WPB, (lds_ptr<R>)(sh + (wv * 4 + g) * LSZ), FORWARD)
+// ... and its launch: a wave per four trajectories, WPB of them per workgroup (XCD: the single-wave placement grid), `rows` grid rows
+template <int WPB, bool XCD = false, class K, class... A>
+static int launch_quad(K kernel, const int B, const unsigned rows, void* stream, const A&... args) {
+  const unsigned blocks = XCD ? xcd_blocks(B) : (unsigned)(((long)B + 4 * WPB - 1) / (4 * WPB));
+  hipLaunchKernelGGL(kernel, dim3(blocks, rows), dim3(64 * WPB), 0, (hipStream_t)stream, args...);
+  return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
+}
+#endif
+// Which instantiation of a quad kernel serves a problem: f(GENERAL, LEANQ) with the two as std::bool_constant. GENERAL: cubature weights
+// with lam != 0, for the models that have the variant (quad_general_exists; Impl::quad_supported has checked) -- I2C_ENOTSUP for the
+// others; unit weights (lam = 0, every shipped config) run the plain one. LEANQ: no optional output asked for, in the kernels that
+// have a lean variant (HAS_LEAN; the others are only ever instantiated with LEANQ = false).
+template <class M, bool HAS_LEAN, class F> static int quad_variant(const bool unit, const bool lean, const F& f) {
+  if (!unit) {
+    if constexpr (quad_general_exists<M>()) {
+      if constexpr (HAS_LEAN) {
+        if (lean) return f(std::true_type{}, std::true_type{});
+      }
+      return f(std::true_type{}, std::false_type{});
+    } else {
+      return I2C_ENOTSUP;
+    }
+  }
+  if constexpr (HAS_LEAN) {
+    if (lean) return f(std::false_type{}, std::true_type{});
+  }
+  return f(std::false_type{}, std::false_type{});
+}
+
+// the quad forward sweep (forward_quad_body)
+#ifndef I2C_HOST_SIM
 #ifndef I2C_QF_ATTR  // (experiment knob: extra attributes of the quad forward kernel, e.g. __attribute__((amdgpu_waves_per_eu(1, 1))))
 #define I2C_QF_ATTR
 #endif
 template <class M, typename R, typename S, class A, bool GENERAL = false>
 __global__ __launch_bounds__(64 * quad_waves_per_block<M>(), 2) I2C_QF_ATTR void k_quad_forward(const Consts<M, R> c, const A a) {
-  constexpr int WPB = quad_waves_per_block<M>();
-  __shared__ QConst<M, R> kc;
-  __shared__ R sh[WPB * 4 * QG<M>::SIZE];
-  qconst_fill<M, R>(kc, (const Consts<M, R>*)__builtin_amdgcn_kernarg_segment_ptr(), (int)threadIdx.x, 64 * WPB);
-  __syncthreads();
-  const int l = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6), g = (l >> 2) & 3;
-  long b0;
-  if constexpr (WPB == 1) {
-    // A wave reads four consecutive trajectories (32 bytes) of every [B]-contiguous row: the four waves that share a 128-byte line
-    // of each row are mapped onto workgroups of the SAME XCD (workgroups are dealt round-robin over the 8 XCDs, so blocks i and
-    // i + 8 share an L2). Placement is a speed heuristic only -- any mapping computes the same result.
-    const unsigned i = blockIdx.x, x = i & 7u, rr = (i >> 3) & 3u, gg = i >> 5;
-    b0 = 16L * (gg * 8u + x) + 4 * rr;
-  } else {  // (the waves of a workgroup take consecutive groups of four trajectories: one 128-byte line of a [B]-contiguous row)
-    b0 = 4L * ((long)blockIdx.x * WPB + wv);
-  }
-#ifdef I2C_QUAD_PLACEMENT  // (diagnostic build, never shipped: where the dispatcher put this wave -- tools/placement_summary.py)
-  if (l == 0)
-    printf("placement %u %d %u %u\n", blockIdx.x, b0 < c.B ? 1 : 0, (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4),
-           (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20));
-#endif
-  if (b0 >= c.B) return;  // (wave-uniform: no trajectory in this wave)
-  const long b = b0 + g;
-#ifdef I2C_QF_NOSTORE  // (experiment, never shipped: the sweep without its stores -- how much of it is the store path)
-  const bool live = false;
-#else
-  const bool live = b < c.B;
-#endif
-  const Quad<R> q{l, l >> 4, g, l & 3, (lds_ptr<R>)(sh + (wv * 4 + g) * QG<M>::SIZE)};
-  forward_quad_body<M, R, S, GENERAL>(c, kc, a, (int)(b < c.B ? b : c.B - 1), live, q);
-}
-template <class M, typename R, typename S, bool GENERAL, class A>
-static int launch_quad_forward_g(const Consts<M, R>& c, const A& a, void* stream) {
-  constexpr int WPB = quad_waves_per_block<M>();
-  const unsigned blocks = WPB == 1 ? (unsigned)(((long)c.B + 127) / 128) * 32u : (unsigned)(((long)c.B + 4 * WPB - 1) / (4 * WPB));
-  hipLaunchKernelGGL((k_quad_forward<M, R, S, A, GENERAL>), dim3(blocks), dim3(64 * WPB), 0, (hipStream_t)stream, c, a);
-  return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
+  I2C_QUAD_SETUP(quad_waves_per_block<M>(), QG<M>::SIZE, true, QConst<M, R>)
+  forward_quad_body<M, R, S, GENERAL>(c, kc, a, b, live, q);
 }
 #endif
-// unit weights (lam = 0, every shipped config), or the GENERAL variant where the model has it (Impl::quad_supported has checked)
 template <class M, typename R, typename S, class A>
 static int launch_quad_forward(const Consts<M, R>& c, const A& a, void* stream) {
-  const bool unit = c.rule_xu.unit && c.rule_x.unit && c.rule_xu.w0 == R(0) && c.rule_x.w0 == R(0);
-  if constexpr (quad_general_exists<M>()) {
-    if (!unit) return launch_quad_forward_g<M, R, S, true>(c, a, stream);
-  }
-  return unit ? launch_quad_forward_g<M, R, S, false>(c, a, stream) : I2C_ENOTSUP;
+  return quad_variant<M, false>(unit_rule(c), false, [&](auto general, auto) {
+    constexpr bool GENERAL = decltype(general)::value;
+#ifdef I2C_HOST_SIM
+    return sim_quad<QConst<M, R>>(c, (const R*)nullptr, QG<M>::SIZE, 0, [&](const auto& kc, const int b, const bool live, const Quad<R>& q, int) {
+      forward_quad_body<M, R, S, GENERAL>(c, kc, a, b, live, q);
+    });
+#else
+    constexpr int WPB = quad_waves_per_block<M>();
+    return launch_quad<WPB, WPB == 1>(k_quad_forward<M, R, S, A, GENERAL>, c.B, 1u, stream, c, a);
+#endif
+  });
 }
 
 // the quad backward sweep: d = 16 models with identity observations (backward_quad_body, trajectory-major buffers), and -- round 6 --
@@ -465,341 +550,140 @@ I2C_FN void quad_backward_dispatch(const Consts<M, R>& c, const KC& kc, const A&
   if constexpr (QG<M>::WIDE) backward_quad_body<M, R, S, GENERAL>(c, kc, a, b, live, q);
   else backward_quad8_body<M, R, S, GENERAL, LEANQ>(c, kc, a, b, live, q);
 }
-#ifdef I2C_HOST_SIM
-template <class M, typename R, typename S, bool GENERAL, bool LEANQ, class A>
-static int launch_quad_backward_g(const Consts<M, R>& c, const A& a, void*) {
-  QBConst<M, R> kc;
-  qbconst_fill<M, R>(kc, &c, 0, 1);
-  constexpr int LSZ = quad_backward_lds<M>();
-  for (int b0 = 0; b0 < c.B; b0 += 4) {
-    std::vector<R> sh((size_t)4 * LSZ, R(0)), xch(128, R(0));
-    HostBarrier bar(64);
-    std::vector<std::thread> lanes;
-    for (int l = 0; l < 64; ++l)
-      lanes.emplace_back([&, l, b0] {
-        const int g = (l >> 2) & 3, b = b0 + g;
-        const bool live = b < c.B;
-        quad_backward_dispatch<M, R, S, GENERAL, LEANQ>(c, kc, a, live ? b : c.B - 1, live, Quad<R>{l, l >> 4, g, l & 3, sh.data() + g * LSZ, &bar, xch.data()});
-      });
-    for (auto& th : lanes) th.join();
-  }
-  return I2C_OK;
-}
-#else
-constexpr int QB_WAVES_PER_BLOCK = 4;
+#ifndef I2C_HOST_SIM
 template <class M, typename R, typename S, class A, bool GENERAL = false, bool LEANQ = false>
 __global__ __launch_bounds__(64 * QB_WAVES_PER_BLOCK, 2) void k_quad_backward(const Consts<M, R> c, const A a) {
-  constexpr int WPB = QB_WAVES_PER_BLOCK, LSZ = quad_backward_lds<M>();
-  __shared__ QBConst<M, R> kc;
-  __shared__ R sh[WPB * 4 * LSZ];
-  qbconst_fill<M, R>(kc, (const Consts<M, R>*)__builtin_amdgcn_kernarg_segment_ptr(), (int)threadIdx.x, 64 * WPB);
-  __syncthreads();
-  const int l = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6), g = (l >> 2) & 3;
-  // d = 16: trajectory-major buffers, nothing is shared between waves. d <= 8: the four waves of a workgroup take consecutive
-  // groups of four trajectories -- together one 128-byte line of every [B]-contiguous row (as k_quad_forward)
-  const long b0 = 4L * ((long)blockIdx.x * WPB + wv);
-  if (b0 >= c.B) return;  // (wave-uniform: no trajectory in this wave)
-  const long b = b0 + g;
-  const bool live = b < c.B;
-  const Quad<R> q{l, l >> 4, g, l & 3, (lds_ptr<R>)(sh + (wv * 4 + g) * LSZ)};
-  quad_backward_dispatch<M, R, S, GENERAL, LEANQ>(c, kc, a, (int)(live ? b : c.B - 1), live, q);
-}
-template <class M, typename R, typename S, bool GENERAL, bool LEANQ, class A>
-static int launch_quad_backward_g(const Consts<M, R>& c, const A& a, void* stream) {
-  constexpr int WPB = QB_WAVES_PER_BLOCK;
-  hipLaunchKernelGGL((k_quad_backward<M, R, S, A, GENERAL, LEANQ>), dim3((unsigned)(((long)c.B + 4 * WPB - 1) / (4 * WPB))), dim3(64 * WPB), 0, (hipStream_t)stream, c, a);
-  return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
+  I2C_QUAD_SETUP(QB_WAVES_PER_BLOCK, quad_backward_lds<M>(), false, QBConst<M, R>)
+  quad_backward_dispatch<M, R, S, GENERAL, LEANQ>(c, kc, a, b, live, q);
 }
 #endif
-// unit weights (lam = 0, every shipped config), or the GENERAL variant where the model has it (Impl::quad_supported has checked);
 // d <= 8: the lean variant when no optional output is asked for
 template <class M, typename R, typename S, class A>
 static int launch_quad_backward(const Consts<M, R>& c, const A& a, void* stream) {
-  const bool unit = c.rule_xu.unit && c.rule_x.unit && c.rule_xu.w0 == R(0) && c.rule_x.w0 == R(0);
-  if constexpr (QG<M>::WIDE) {
-    if constexpr (quad_general_exists<M>()) {
-      if (!unit) return launch_quad_backward_g<M, R, S, true, false>(c, a, stream);
-    }
-    return unit ? launch_quad_backward_g<M, R, S, false, false>(c, a, stream) : I2C_ENOTSUP;
-  } else {
-    const bool lean = !a.xm && !a.zpost && !a.cell_stats;
-    if constexpr (quad_general_exists<M>()) {
-      if (!unit) return lean ? launch_quad_backward_g<M, R, S, true, true>(c, a, stream) : launch_quad_backward_g<M, R, S, true, false>(c, a, stream);
-    }
-    if (!unit) return I2C_ENOTSUP;
-    return lean ? launch_quad_backward_g<M, R, S, false, true>(c, a, stream) : launch_quad_backward_g<M, R, S, false, false>(c, a, stream);
-  }
+  return quad_variant<M, !QG<M>::WIDE>(unit_rule(c), !a.xm && !a.zpost && !a.cell_stats, [&](auto general, auto leanq) {
+    constexpr bool GENERAL = decltype(general)::value, LEANQ = decltype(leanq)::value;
+#ifdef I2C_HOST_SIM
+    return sim_quad<QBConst<M, R>>(c, (const R*)nullptr, quad_backward_lds<M>(), 0, [&](const auto& kc, const int b, const bool live, const Quad<R>& q, int) {
+      quad_backward_dispatch<M, R, S, GENERAL, LEANQ>(c, kc, a, b, live, q);
+    });
+#else
+    return launch_quad<QB_WAVES_PER_BLOCK>(k_quad_backward<M, R, S, A, GENERAL, LEANQ>, c.B, 1u, stream, c, a);
+#endif
+  });
 }
 
-// the quad WALKER of the chunked schedule (d <= 8; backward_quad8_body<CHUNK>): grid = groups of four trajectories x chunks
-template <class M, typename R, typename S> static QChunk<R> quad_chunk_of(const Consts<M, R>& c, const ChunkArgs<R, S>& a, const int ch) {
+// the chunked schedule in the quad form (d <= 8): the WALKER (backward_quad8_body<QB8_CHUNK_WALK>: grid = groups of four trajectories x
+// chunks), the COMPOSE and the STITCH pass (compose_quad8_body, backward_quad8_body<QB8_STITCH>)
+template <class M, typename R, typename S> I2C_FN QChunk<R> quad_chunk_of(const Consts<M, R>& c, const ChunkArgs<R, S>& a, const int ch) {
   const int t_lo = ch * a.chunk_len, t_hi = (t_lo + a.chunk_len < c.T) ? t_lo + a.chunk_len : c.T;
   return QChunk<R>{a.bnd, a.part, ch, t_lo, t_hi, a.comp, a.n_chunks};
 }
-#ifdef I2C_HOST_SIM
-template <class M, typename R, typename S, bool GENERAL, bool LEANQ>
-static int launch_quad_chunk_walk_g(const Consts<M, R>& c, const ChunkArgs<R, S>& a, void*) {
-  if constexpr (!QG<M>::WIDE) {
-    QBConst<M, R> kc;
-    qbconst_fill<M, R>(kc, &c, 0, 1);
-    constexpr int LSZ = quad_backward_lds<M>();
-    for (int b0 = 0; b0 < c.B; b0 += 4) {  // (the simulated wavefront of a group walks its chunks one after the other: 64 threads per group)
-      std::vector<R> sh((size_t)4 * LSZ, R(0)), xch(128, R(0));
-      HostBarrier bar(64);
-      std::vector<std::thread> lanes;
-      for (int l = 0; l < 64; ++l)
-        lanes.emplace_back([&, l, b0] {
-          const int g = (l >> 2) & 3, b = b0 + g;
-          const bool live = b < c.B;
-          for (int ch = 0; ch < a.n_chunks; ++ch)
-            backward_quad8_body<M, R, S, GENERAL, LEANQ, QB8_CHUNK_WALK>(c, kc, a.cell, live ? b : c.B - 1, live,
-                                                               Quad<R>{l, l >> 4, g, l & 3, sh.data() + g * LSZ, &bar, xch.data()},
-                                                               quad_chunk_of<M, R, S>(c, a, ch));
-        });
-      for (auto& th : lanes) th.join();
-    }
-    return I2C_OK;
-  }
-  return I2C_ENOTSUP;
-}
-// the COMPOSE and STITCH passes in the quad form (compose_quad8_body, backward_quad8_body<QB8_STITCH>)
-template <class M, typename R, typename S>
-static int launch_quad_chunk_compose(const Consts<M, R>& c, const ChunkArgs<R, S>& a, void*) {
-  if constexpr (!QG<M>::WIDE) {
-    for (int b0 = 0; b0 < c.B; b0 += 4) {
-      std::vector<R> xch(128, R(0));
-      HostBarrier bar(64);
-      std::vector<std::thread> lanes;
-      for (int l = 0; l < 64; ++l)
-        lanes.emplace_back([&, l, b0] {
-          const int g = (l >> 2) & 3, b = b0 + g;
-          const bool live = b < c.B;
-          for (int ch = 0; ch < a.n_chunks; ++ch) {
-            const QChunk<R> qc = quad_chunk_of<M, R, S>(c, a, ch);
-            compose_quad8_body<M, R, S>(c, a.cell.fwd, a.comp, ch, qc.t_lo, qc.t_hi, live ? b : c.B - 1, live, Quad<R>{l, l >> 4, g, l & 3, nullptr, &bar, xch.data()});
-          }
-        });
-      for (auto& th : lanes) th.join();
-    }
-    return I2C_OK;
-  }
-  return I2C_ENOTSUP;
-}
-template <class M, typename R, typename S, bool GENERAL>
-static int launch_quad_chunk_stitch_g(const Consts<M, R>& c, const ChunkArgs<R, S>& a, void*) {
-  if constexpr (!QG<M>::WIDE) {
-    QBConst<M, R> kc;
-    qbconst_fill<M, R>(kc, &c, 0, 1);
-    constexpr int LSZ = quad_backward_lds<M>();
-    for (int b0 = 0; b0 < c.B; b0 += 4) {
-      std::vector<R> sh((size_t)4 * LSZ, R(0)), xch(128, R(0));
-      HostBarrier bar(64);
-      std::vector<std::thread> lanes;
-      for (int l = 0; l < 64; ++l)
-        lanes.emplace_back([&, l, b0] {
-          const int g = (l >> 2) & 3, b = b0 + g;
-          const bool live = b < c.B;
-          backward_quad8_body<M, R, S, GENERAL, true, QB8_STITCH>(c, kc, a.cell, live ? b : c.B - 1, live,
-                                                                  Quad<R>{l, l >> 4, g, l & 3, sh.data() + g * LSZ, &bar, xch.data()}, quad_chunk_of<M, R, S>(c, a, 0));
-        });
-      for (auto& th : lanes) th.join();
-    }
-    return I2C_OK;
-  }
-  return I2C_ENOTSUP;
-}
-#else
+#ifndef I2C_HOST_SIM
 template <class M, typename R, typename S>
 __global__ __launch_bounds__(64 * QB_WAVES_PER_BLOCK, 2) void k_quad_chunk_compose(const Consts<M, R> c, const ChunkArgs<R, S> a) {
-  constexpr int WPB = QB_WAVES_PER_BLOCK;
-  const int l = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6), g = (l >> 2) & 3;
-  const long b0 = 4L * ((long)blockIdx.x * WPB + wv);
-  if (b0 >= c.B) return;  // (wave-uniform: no trajectory in this wave)
-  const long b = b0 + g;
-  const bool live = b < c.B;
-  const Quad<R> q{l, l >> 4, g, l & 3, (lds_ptr<R>)nullptr};
-  const int ch = (int)blockIdx.y, t_lo = ch * a.chunk_len, t_hi = (t_lo + a.chunk_len < c.T) ? t_lo + a.chunk_len : c.T;
-  compose_quad8_body<M, R, S>(c, a.cell.fwd, a.comp, ch, t_lo, t_hi, (int)(live ? b : c.B - 1), live, q);
-}
-template <class M, typename R, typename S>
-static int launch_quad_chunk_compose(const Consts<M, R>& c, const ChunkArgs<R, S>& a, void* stream) {
-  if constexpr (!QG<M>::WIDE) {
-    constexpr int WPB = QB_WAVES_PER_BLOCK;
-    hipLaunchKernelGGL((k_quad_chunk_compose<M, R, S>), dim3((unsigned)(((long)c.B + 4 * WPB - 1) / (4 * WPB)), (unsigned)a.n_chunks), dim3(64 * WPB), 0, (hipStream_t)stream, c, a);
-    return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
-  }
-  return I2C_ENOTSUP;
+  I2C_QUAD_LANE(QB_WAVES_PER_BLOCK, (lds_ptr<R>)nullptr, false)
+  const QChunk<R> qc = quad_chunk_of<M, R, S>(c, a, (int)blockIdx.y);
+  compose_quad8_body<M, R, S>(c, a.cell.fwd, a.comp, qc.ch, qc.t_lo, qc.t_hi, b, live, q);
 }
 template <class M, typename R, typename S, bool GENERAL = false>
 __global__ __launch_bounds__(64 * QB_WAVES_PER_BLOCK, 2) void k_quad_chunk_stitch(const Consts<M, R> c, const ChunkArgs<R, S> a) {
-  constexpr int WPB = QB_WAVES_PER_BLOCK, LSZ = quad_backward_lds<M>();
-  __shared__ QBConst<M, R> kc;
-  __shared__ R sh[WPB * 4 * LSZ];
-  qbconst_fill<M, R>(kc, (const Consts<M, R>*)__builtin_amdgcn_kernarg_segment_ptr(), (int)threadIdx.x, 64 * WPB);
-  __syncthreads();
-  const int l = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6), g = (l >> 2) & 3;
-  const long b0 = 4L * ((long)blockIdx.x * WPB + wv);
-  if (b0 >= c.B) return;  // (wave-uniform: no trajectory in this wave)
-  const long b = b0 + g;
-  const bool live = b < c.B;
-  const Quad<R> q{l, l >> 4, g, l & 3, (lds_ptr<R>)(sh + (wv * 4 + g) * LSZ)};
-  backward_quad8_body<M, R, S, GENERAL, true, QB8_STITCH>(c, kc, a.cell, (int)(live ? b : c.B - 1), live, q, QChunk<R>{a.bnd, a.part, 0, 0, c.T, a.comp, a.n_chunks});
-}
-template <class M, typename R, typename S, bool GENERAL>
-static int launch_quad_chunk_stitch_g(const Consts<M, R>& c, const ChunkArgs<R, S>& a, void* stream) {
-  if constexpr (!QG<M>::WIDE) {
-    constexpr int WPB = QB_WAVES_PER_BLOCK;
-    hipLaunchKernelGGL((k_quad_chunk_stitch<M, R, S, GENERAL>), dim3((unsigned)(((long)c.B + 4 * WPB - 1) / (4 * WPB))), dim3(64 * WPB), 0, (hipStream_t)stream, c, a);
-    return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
-  }
-  return I2C_ENOTSUP;
+  I2C_QUAD_SETUP(QB_WAVES_PER_BLOCK, quad_backward_lds<M>(), false, QBConst<M, R>)
+  backward_quad8_body<M, R, S, GENERAL, true, QB8_STITCH>(c, kc, a.cell, b, live, q, QChunk<R>{a.bnd, a.part, 0, 0, c.T, a.comp, a.n_chunks});
 }
 template <class M, typename R, typename S, bool GENERAL = false, bool LEANQ = false>
 __global__ __launch_bounds__(64 * QB_WAVES_PER_BLOCK, 2) void k_quad_chunk_walk(const Consts<M, R> c, const ChunkArgs<R, S> a) {
-  constexpr int WPB = QB_WAVES_PER_BLOCK, LSZ = quad_backward_lds<M>();
-  __shared__ QBConst<M, R> kc;
-  __shared__ R sh[WPB * 4 * LSZ];
-  qbconst_fill<M, R>(kc, (const Consts<M, R>*)__builtin_amdgcn_kernarg_segment_ptr(), (int)threadIdx.x, 64 * WPB);
-  __syncthreads();
-  const int l = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6), g = (l >> 2) & 3;
-  const long b0 = 4L * ((long)blockIdx.x * WPB + wv);
-  if (b0 >= c.B) return;  // (wave-uniform: no trajectory in this wave)
-  const long b = b0 + g;
-  const bool live = b < c.B;
-  const Quad<R> q{l, l >> 4, g, l & 3, (lds_ptr<R>)(sh + (wv * 4 + g) * LSZ)};
-  const int ch = (int)blockIdx.y, t_lo = ch * a.chunk_len, t_hi = (t_lo + a.chunk_len < c.T) ? t_lo + a.chunk_len : c.T;
-  backward_quad8_body<M, R, S, GENERAL, LEANQ, QB8_CHUNK_WALK>(c, kc, a.cell, (int)(live ? b : c.B - 1), live, q, QChunk<R>{a.bnd, a.part, ch, t_lo, t_hi, a.comp, a.n_chunks});
-}
-template <class M, typename R, typename S, bool GENERAL, bool LEANQ>
-static int launch_quad_chunk_walk_g(const Consts<M, R>& c, const ChunkArgs<R, S>& a, void* stream) {
-  if constexpr (!QG<M>::WIDE) {
-    constexpr int WPB = QB_WAVES_PER_BLOCK;
-    hipLaunchKernelGGL((k_quad_chunk_walk<M, R, S, GENERAL, LEANQ>), dim3((unsigned)(((long)c.B + 4 * WPB - 1) / (4 * WPB)), (unsigned)a.n_chunks), dim3(64 * WPB), 0,
-                       (hipStream_t)stream, c, a);
-    return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
-  }
-  return I2C_ENOTSUP;
+  I2C_QUAD_SETUP(QB_WAVES_PER_BLOCK, quad_backward_lds<M>(), false, QBConst<M, R>)
+  backward_quad8_body<M, R, S, GENERAL, LEANQ, QB8_CHUNK_WALK>(c, kc, a.cell, b, live, q, quad_chunk_of<M, R, S>(c, a, (int)blockIdx.y));
 }
 #endif
 template <class M, typename R, typename S>
-static int launch_quad_chunk_stitch(const Consts<M, R>& c, const ChunkArgs<R, S>& a, void* stream) {
-  const bool unit = c.rule_xu.unit && c.rule_x.unit && c.rule_xu.w0 == R(0) && c.rule_x.w0 == R(0);
-  if constexpr (quad_general_exists<M>()) {
-    if (!unit) return launch_quad_chunk_stitch_g<M, R, S, true>(c, a, stream);
+static int launch_quad_chunk_compose(const Consts<M, R>& c, const ChunkArgs<R, S>& a, void* stream) {
+  if constexpr (!QG<M>::WIDE) {
+#ifdef I2C_HOST_SIM
+    return sim_quad<NoConst>(c, (const R*)nullptr, 0, a.n_chunks, [&](const NoConst&, const int b, const bool live, const Quad<R>& q, const int ch) {
+      const QChunk<R> qc = quad_chunk_of<M, R, S>(c, a, ch);
+      compose_quad8_body<M, R, S>(c, a.cell.fwd, a.comp, ch, qc.t_lo, qc.t_hi, b, live, q);
+    });
+#else
+    return launch_quad<QB_WAVES_PER_BLOCK>(k_quad_chunk_compose<M, R, S>, c.B, (unsigned)a.n_chunks, stream, c, a);
+#endif
   }
-  return unit ? launch_quad_chunk_stitch_g<M, R, S, false>(c, a, stream) : I2C_ENOTSUP;
+  return I2C_ENOTSUP;
+}
+template <class M, typename R, typename S>
+static int launch_quad_chunk_stitch(const Consts<M, R>& c, const ChunkArgs<R, S>& a, void* stream) {
+  if constexpr (!QG<M>::WIDE) {
+    return quad_variant<M, false>(unit_rule(c), false, [&](auto general, auto) {
+      constexpr bool GENERAL = decltype(general)::value;
+#ifdef I2C_HOST_SIM
+      return sim_quad<QBConst<M, R>>(c, (const R*)nullptr, quad_backward_lds<M>(), 0, [&](const auto& kc, const int b, const bool live, const Quad<R>& q, int) {
+        backward_quad8_body<M, R, S, GENERAL, true, QB8_STITCH>(c, kc, a.cell, b, live, q, quad_chunk_of<M, R, S>(c, a, 0));
+      });
+#else
+      return launch_quad<QB_WAVES_PER_BLOCK>(k_quad_chunk_stitch<M, R, S, GENERAL>, c.B, 1u, stream, c, a);
+#endif
+    });
+  }
+  return I2C_ENOTSUP;
 }
 template <class M, typename R, typename S>
 static int launch_quad_chunk_walk(const Consts<M, R>& c, const ChunkArgs<R, S>& a, void* stream) {
-  const bool unit = c.rule_xu.unit && c.rule_x.unit && c.rule_xu.w0 == R(0) && c.rule_x.w0 == R(0);
-  const bool lean = !a.cell.xm && !a.cell.zpost && !a.cell.cell_stats;
-  if constexpr (quad_general_exists<M>()) {
-    if (!unit) return lean ? launch_quad_chunk_walk_g<M, R, S, true, true>(c, a, stream) : launch_quad_chunk_walk_g<M, R, S, true, false>(c, a, stream);
+  if constexpr (!QG<M>::WIDE) {
+    return quad_variant<M, true>(unit_rule(c), !a.cell.xm && !a.cell.zpost && !a.cell.cell_stats, [&](auto general, auto leanq) {
+      constexpr bool GENERAL = decltype(general)::value, LEANQ = decltype(leanq)::value;
+#ifdef I2C_HOST_SIM
+      return sim_quad<QBConst<M, R>>(c, (const R*)nullptr, quad_backward_lds<M>(), a.n_chunks, [&](const auto& kc, const int b, const bool live, const Quad<R>& q, const int ch) {
+        backward_quad8_body<M, R, S, GENERAL, LEANQ, QB8_CHUNK_WALK>(c, kc, a.cell, b, live, q, quad_chunk_of<M, R, S>(c, a, ch));
+      });
+#else
+      return launch_quad<QB_WAVES_PER_BLOCK>(k_quad_chunk_walk<M, R, S, GENERAL, LEANQ>, c.B, (unsigned)a.n_chunks, stream, c, a);
+#endif
+    });
   }
-  if (!unit) return I2C_ENOTSUP;
-  return lean ? launch_quad_chunk_walk_g<M, R, S, false, true>(c, a, stream) : launch_quad_chunk_walk_g<M, R, S, false, false>(c, a, stream);
+  return I2C_ENOTSUP;
 }
 
 // the quad propagation (propagate_quad_body): d = 16 models with identity observations
-#ifdef I2C_HOST_SIM
-template <class M, typename R, bool GENERAL>
-static int launch_quad_propagate_g(const Consts<M, R>& c, const PropArgs<R>& a, void*) {
-  QPConst<M, R> kc;
-  qpconst_fill<M, R>(kc, &c, 0, 1);
-  for (int b0 = 0; b0 < c.B; b0 += 4) {
-    std::vector<R> sh((size_t)4 * QG<M>::SIZE, R(0)), xch(128, R(0));
-    HostBarrier bar(64);
-    std::vector<std::thread> lanes;
-    for (int l = 0; l < 64; ++l)
-      lanes.emplace_back([&, l, b0] {
-        const int g = (l >> 2) & 3, b = b0 + g;
-        const bool live = b < c.B;
-        propagate_quad_body<M, R, GENERAL>(c, kc, a, live ? b : c.B - 1, live, Quad<R>{l, l >> 4, g, l & 3, sh.data() + g * QG<M>::SIZE, &bar, xch.data()});
-      });
-    for (auto& th : lanes) th.join();
-  }
-  return I2C_OK;
-}
-#else
+#ifndef I2C_HOST_SIM
 template <class M, typename R, bool GENERAL = false>
 __global__ __launch_bounds__(64 * quad_waves_per_block<M>(), 2) void k_quad_propagate(const Consts<M, R> c, const PropArgs<R> a) {
-  constexpr int WPB = quad_waves_per_block<M>();
-  __shared__ QPConst<M, R> kc;
-  __shared__ R sh[WPB * 4 * QG<M>::SIZE];
-  qpconst_fill<M, R>(kc, (const Consts<M, R>*)__builtin_amdgcn_kernarg_segment_ptr(), (int)threadIdx.x, 64 * WPB);
-  __syncthreads();
-  const int l = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6), g = (l >> 2) & 3;
-  const long b0 = 4L * ((long)blockIdx.x * WPB + wv);
-  if (b0 >= c.B) return;  // (wave-uniform: no trajectory in this wave)
-  const long b = b0 + g;
-  const bool live = b < c.B;
-  const Quad<R> q{l, l >> 4, g, l & 3, (lds_ptr<R>)(sh + (wv * 4 + g) * QG<M>::SIZE)};
-  propagate_quad_body<M, R, GENERAL>(c, kc, a, (int)(live ? b : c.B - 1), live, q);
-}
-template <class M, typename R, bool GENERAL>
-static int launch_quad_propagate_g(const Consts<M, R>& c, const PropArgs<R>& a, void* stream) {
-  constexpr int WPB = quad_waves_per_block<M>();
-  hipLaunchKernelGGL((k_quad_propagate<M, R, GENERAL>), dim3((unsigned)(((long)c.B + 4 * WPB - 1) / (4 * WPB))), dim3(64 * WPB), 0, (hipStream_t)stream, c, a);
-  return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
+  I2C_QUAD_SETUP(quad_waves_per_block<M>(), QG<M>::SIZE, false, QPConst<M, R>)
+  propagate_quad_body<M, R, GENERAL>(c, kc, a, b, live, q);
 }
 #endif
 // unit weights, or (round 6) the GENERAL variant: any CubatureQuadrature(alpha, beta, kappa)
 template <class M, typename R>
 static int launch_quad_propagate(const Consts<M, R>& c, const PropArgs<R>& a, void* stream) {
-  const bool unit = c.rule_xu.unit && c.rule_xu.w0 == R(0);
-  if constexpr (quad_general_exists<M>()) {
-    if (!unit) return launch_quad_propagate_g<M, R, true>(c, a, stream);
-  }
-  return unit ? launch_quad_propagate_g<M, R, false>(c, a, stream) : I2C_ENOTSUP;
+  return quad_variant<M, false>(unit_rule(c.rule_xu), false, [&](auto general, auto) {
+    constexpr bool GENERAL = decltype(general)::value;
+#ifdef I2C_HOST_SIM
+    return sim_quad<QPConst<M, R>>(c, (const R*)nullptr, QG<M>::SIZE, 0, [&](const auto& kc, const int b, const bool live, const Quad<R>& q, int) {
+      propagate_quad_body<M, R, GENERAL>(c, kc, a, b, live, q);
+    });
+#else
+    return launch_quad<quad_waves_per_block<M>()>(k_quad_propagate<M, R, GENERAL>, c.B, 1u, stream, c, a);
+#endif
+  });
 }
 
 // the quad filter step (ckf_quad_body): d = 16 models
-#ifdef I2C_HOST_SIM
-template <class M, typename R>
-static int launch_quad_ckf(const Consts<M, R>& c, const ZetaArg<M, R>& zeta, const CkfArgs<R>& a, void*) {
-  QKConst<M, R> kc;
-  qkconst_fill<M, R>(kc, &c, zeta.v, 0, 1);
-  for (int b0 = 0; b0 < c.B; b0 += 4) {
-    std::vector<R> sh((size_t)4 * QG<M>::SIZE, R(0)), xch(128, R(0));
-    HostBarrier bar(64);
-    std::vector<std::thread> lanes;
-    for (int l = 0; l < 64; ++l)
-      lanes.emplace_back([&, l, b0] {
-        const int g = (l >> 2) & 3, b = b0 + g;
-        const bool live = b < c.B;
-        ckf_quad_body<M, R>(c, kc, a, live ? b : c.B - 1, live, Quad<R>{l, l >> 4, g, l & 3, sh.data() + g * QG<M>::SIZE, &bar, xch.data()});
-      });
-    for (auto& th : lanes) th.join();
-  }
-  return I2C_OK;
-}
-#else
+#ifndef I2C_HOST_SIM
 template <class M, typename R>
 __global__ __launch_bounds__(64 * quad_waves_per_block<M>(), 2) void k_quad_ckf(const Consts<M, R> c, const ZetaArg<M, R> zeta, const CkfArgs<R> a) {
-  constexpr int WPB = quad_waves_per_block<M>();
-  __shared__ QKConst<M, R> kc;
-  __shared__ R sh[WPB * 4 * QG<M>::SIZE];
-  {  // (`c` is the first kernel parameter, `zeta` follows it at its natural alignment: see k_group)
-    const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t zoff = (sizeof(Consts<M, R>) + alignof(ZetaArg<M, R>) - 1) / alignof(ZetaArg<M, R>) * alignof(ZetaArg<M, R>);
-    qkconst_fill<M, R>(kc, (const Consts<M, R>*)ka, ((const ZetaArg<M, R>*)(ka + zoff))->v, (int)threadIdx.x, 64 * WPB);
-  }
-  __syncthreads();
-  const int l = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6), g = (l >> 2) & 3;
-  const long b0 = 4L * ((long)blockIdx.x * WPB + wv);
-  if (b0 >= c.B) return;  // (wave-uniform: no trajectory in this wave)
-  const long b = b0 + g;
-  const bool live = b < c.B;
-  const Quad<R> q{l, l >> 4, g, l & 3, (lds_ptr<R>)(sh + (wv * 4 + g) * QG<M>::SIZE)};
-  ckf_quad_body<M, R>(c, kc, a, (int)(live ? b : c.B - 1), live, q);
-}
-template <class M, typename R>
-static int launch_quad_ckf(const Consts<M, R>& c, const ZetaArg<M, R>& zeta, const CkfArgs<R>& a, void* stream) {
-  constexpr int WPB = quad_waves_per_block<M>();
-  hipLaunchKernelGGL((k_quad_ckf<M, R>), dim3((unsigned)(((long)c.B + 4 * WPB - 1) / (4 * WPB))), dim3(64 * WPB), 0, (hipStream_t)stream, c, zeta, a);
-  return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
+  I2C_QUAD_SETUP(quad_waves_per_block<M>(), QG<M>::SIZE, false, QKConst<M, R>)  // (kc: with `zeta`, the second parameter)
+  ckf_quad_body<M, R>(c, kc, a, b, live, q);
 }
 #endif
+template <class M, typename R>
+static int launch_quad_ckf(const Consts<M, R>& c, const ZetaArg<M, R>& zeta, const CkfArgs<R>& a, void* stream) {
+#ifdef I2C_HOST_SIM
+  return sim_quad<QKConst<M, R>>(c, zeta.v, QG<M>::SIZE, 0, [&](const auto& kc, const int b, const bool live, const Quad<R>& q, int) {
+    ckf_quad_body<M, R>(c, kc, a, b, live, q);
+  });
+#else
+  return launch_quad<quad_waves_per_block<M>()>(k_quad_ckf<M, R>, c.B, 1u, stream, c, zeta, a);
+#endif
+}
 
 template <int KIND, class M, typename R, typename S, class A>
 static int launch_wave(const Consts<M, R>& c, const A& a, void* stream) {
@@ -914,55 +798,54 @@ static void chunk_geometry(int B, int T, int* n_chunks, int* chunk_len) {
   *chunk_len = len;
   *n_chunks = (T + len - 1) / len;
 }
+// The workspace of the chunked schedules (I2cProblem.work), as element offsets: the composite maps [NC][NX + NX*NX + sym(NX)][B] at 0,
+// behind them the smoothed states entering the chunks [NC][NX + sym(NX)][B] and the per-chunk cost sums [NC][3][B]
+template <class M> struct ChunkWork {
+  size_t bnd, part, total;
+  ChunkWork(const int B, const int n_chunks) {
+    constexpr int NX = M::NX;
+    const size_t n = (size_t)n_chunks * (size_t)B;
+    bnd = n * (NX + NX * NX + sym(NX));
+    part = bnd + n * (NX + sym(NX));
+    total = part + n * 3;  // (3: the Linearize form's partial sums)
+  }
+};
 template <class M> static size_t workspace_elems(int B, int T) {
   int nc, len;
   chunk_geometry(B, T, &nc, &len);
-  constexpr int NX = M::NX;
-  return (size_t)nc * (size_t)B * (size_t)((NX + NX * NX + sym(NX)) + (NX + sym(NX)) + 3);  // (3: the Linearize form's partial sums)
+  return ChunkWork<M>(B, nc).total;
+}
+// the arguments of a chunked schedule's passes: the geometry of this batch and its workspace carved
+template <class M, typename R, typename S> static ChunkArgs<R, S> chunk_args(const I2cProblem* p, const CellArgs<R, S>& a) {
+  ChunkArgs<R, S> ch{a, (R*)p->work, nullptr, nullptr, 0, 0};
+  chunk_geometry(p->B, p->T, &ch.n_chunks, &ch.chunk_len);
+  const ChunkWork<M> w(p->B, ch.n_chunks);
+  ch.bnd = ch.comp + w.bnd;
+  ch.part = ch.comp + w.part;
+  return ch;
 }
 
+// ONE detection helper for the batch sizes a model may set for itself (measured per model, i2c_models.hpp): name<M>::value is M::MEMBER
+// where the model declares it, DEFAULT otherwise
+#define I2C_MODEL_CONST(name, MEMBER, DEFAULT)                                                                      \
+  template <class M, class = void> struct name : std::integral_constant<int, (DEFAULT)> {};                         \
+  template <class M> struct name<M, std::void_t<decltype(M::MEMBER)>> : std::integral_constant<int, M::MEMBER> {};
 // batch size from which I2C_BWD_AUTO runs the fused walk: the model's own measured crossover, or the library-wide default
-template <class M, class = void> struct bwd_fused_min_b {
-  static constexpr int value = I2C_BWD_FUSED_MIN_B;
-};
-template <class M> struct bwd_fused_min_b<M, std::void_t<decltype(M::BWD_FUSED_MIN_B)>> {
-  static constexpr int value = M::BWD_FUSED_MIN_B;
-};
-
-// batch window in which the d <= 8 quad backward sweep is the model's DEFAULT (measured per model, i2c_models.hpp:
-// QUAD_BACKWARD8_MIN_B / _MAX_B); models without the pair: on request only
-template <class M, class = void> struct quad_backward_window {
-  static constexpr int min_b = 0, max_b = -1;
-};
-template <class M> struct quad_backward_window<M, std::void_t<decltype(M::QUAD_BACKWARD8_MAX_B)>> {
-  static constexpr int min_b = M::QUAD_BACKWARD8_MIN_B, max_b = M::QUAD_BACKWARD8_MAX_B;
-};
-
-// batch window in which the chunked schedule's WALK pass runs on the quad walker by default (backward_quad8_body<CHUNK>; measured per
-// model, i2c_models.hpp: QUAD_CHUNK_WALK_MIN_B / _MAX_B); models without the pair: on request only (group_lanes = 64 + "chunked")
-template <class M, class = void> struct quad_chunk_walk_window {
-  static constexpr int min_b = 0, max_b = -1;
-};
-template <class M> struct quad_chunk_walk_window<M, std::void_t<decltype(M::QUAD_CHUNK_WALK_MAX_B)>> {
-  static constexpr int min_b = M::QUAD_CHUNK_WALK_MIN_B, max_b = M::QUAD_CHUNK_WALK_MAX_B;
-};
-
+I2C_MODEL_CONST(bwd_fused_min_b, BWD_FUSED_MIN_B, I2C_BWD_FUSED_MIN_B)
+// batch window in which the d <= 8 quad backward sweep is the model's DEFAULT; models without the pair: on request only
+I2C_MODEL_CONST(quad_backward_min_b, QUAD_BACKWARD8_MIN_B, 0)
+I2C_MODEL_CONST(quad_backward_max_b, QUAD_BACKWARD8_MAX_B, -1)
+// batch window in which the chunked schedule's WALK pass runs on the quad walker by default (backward_quad8_body<CHUNK>); models
+// without the pair: on request only (group_lanes = 64 + "chunked")
+I2C_MODEL_CONST(quad_chunk_walk_min_b, QUAD_CHUNK_WALK_MIN_B, 0)
+I2C_MODEL_CONST(quad_chunk_walk_max_b, QUAD_CHUNK_WALK_MAX_B, -1)
 // batch window in which the COMPOSE and STITCH passes of the chunked schedule run in the quad form by default (compose_quad8_body,
-// backward_quad8_body<QB8_STITCH>; measured per model, i2c_models.hpp: QUAD_CHUNK_PASSES_MIN_B / _MAX_B); whatever walker follows
-template <class M, class = void> struct quad_chunk_passes_window {
-  static constexpr int min_b = 0, max_b = -1;
-};
-template <class M> struct quad_chunk_passes_window<M, std::void_t<decltype(M::QUAD_CHUNK_PASSES_MAX_B)>> {
-  static constexpr int min_b = M::QUAD_CHUNK_PASSES_MIN_B, max_b = M::QUAD_CHUNK_PASSES_MAX_B;
-};
-
-// ... and the batch size up to which the STITCH pass alone stays in the quad form (i2c_models.hpp: QUAD_CHUNK_STITCH_MAX_B)
-template <class M, class = void> struct quad_chunk_stitch_window {
-  static constexpr int max_b = -1;
-};
-template <class M> struct quad_chunk_stitch_window<M, std::void_t<decltype(M::QUAD_CHUNK_STITCH_MAX_B)>> {
-  static constexpr int max_b = M::QUAD_CHUNK_STITCH_MAX_B;
-};
+// backward_quad8_body<QB8_STITCH>); whatever walker follows
+I2C_MODEL_CONST(quad_chunk_passes_min_b, QUAD_CHUNK_PASSES_MIN_B, 0)
+I2C_MODEL_CONST(quad_chunk_passes_max_b, QUAD_CHUNK_PASSES_MAX_B, -1)
+// ... and the batch size up to which the STITCH pass alone stays in the quad form
+I2C_MODEL_CONST(quad_chunk_stitch_max_b, QUAD_CHUNK_STITCH_MAX_B, -1)
+#undef I2C_MODEL_CONST
 
 // ---- per-(model, dtype) entry points ------------------------------------------------------
 // Which kernels serve a call:
@@ -1023,7 +906,7 @@ template <class M, typename R, typename S = R> struct Impl {
     } else if (p->inference != I2C_INF_CUBATURE) {
       return I2C_ENOTSUP;
     }  // (a terminal state prior -- covariance control -- is the backward sweep's end of the chain: w_end_of_chain, round 4)
-    if (!c.rule_xu.unit || !c.rule_x.unit || c.rule_xu.w0 != R(0) || c.rule_x.w0 != R(0)) return I2C_ENOTSUP;
+    if (!unit_rule(c)) return I2C_ENOTSUP;
     constexpr long EMAX = C::E_FWD > C::E_POST ? C::E_FWD : C::E_POST;
     if (EMAX * (long)p->B * (long)sizeof(S) >= (1L << 31)) return I2C_EINVAL;
     return window_32bit_ok(p);
@@ -1035,7 +918,7 @@ template <class M, typename R, typename S = R> struct Impl {
   static int quad_supported(const I2cProblem* p, const C& c) {
     if (p->inference != I2C_INF_CUBATURE) return I2C_ENOTSUP;
     // cubature weights with lam != 0 (round 5): the GENERAL variant, for the models that have it (quad_general_exists)
-    if (!quad_general_exists<M>() && (!c.rule_xu.unit || !c.rule_x.unit || c.rule_xu.w0 != R(0) || c.rule_x.w0 != R(0))) return I2C_ENOTSUP;
+    if (!quad_general_exists<M>() && !unit_rule(c)) return I2C_ENOTSUP;
     if constexpr (QG<M>::WIDE) {
       // the d = 16 form addresses trajectory-major buffers only: the posterior / prior in that layout (the engine's default for
       // the wave-capable models) and forward messages that the wave backward sweep reads
@@ -1052,12 +935,12 @@ template <class M, typename R, typename S = R> struct Impl {
   static bool quad_chunk_default(const I2cProblem* p) {
     if constexpr (HAS_QUAD_BACKWARD && !QG<M>::WIDE && LANE)
       return (p->group_lanes == 0 || p->group_lanes == I2C_LANES_QUAD) && p->backward_mode == I2C_BWD_AUTO && p->inference == I2C_INF_CUBATURE &&
-             p->B >= quad_chunk_walk_window<M>::min_b && p->B <= quad_chunk_walk_window<M>::max_b && schedule(p->B, p->T, I2C_BWD_AUTO) == I2C_BWD_CHUNKED;
+             p->B >= quad_chunk_walk_min_b<M>::value && p->B <= quad_chunk_walk_max_b<M>::value && schedule(p->B, p->T, I2C_BWD_AUTO) == I2C_BWD_CHUNKED;
     return false;
   }
   // the compose / stitch passes of the chunked sigma-point schedule: I2C_FAMILY_QUAD when the quad walker was asked for by name
   // (group_lanes = 64 with "chunked": the whole schedule on matrix instructions) or, by default, inside the model's
-  // quad_chunk_passes_window; I2C_FAMILY_LANE otherwise (i2c_kernel_family(problem, I2C_SWEEP_CHUNK_PASSES) reports it)
+  // quad_chunk_passes_min_b .. _max_b; I2C_FAMILY_LANE otherwise (i2c_kernel_family(problem, I2C_SWEEP_CHUNK_PASSES) reports it)
   static int chunk_passes_family(const I2cProblem* p, const C& c) {
     if constexpr (HAS_QUAD_BACKWARD && !QG<M>::WIDE && LANE) {
       // (the composites are addressed through 32-bit offsets of one window per chunk, masked lanes parked at 2 GiB: arithmetic-typed
@@ -1069,7 +952,7 @@ template <class M, typename R, typename S = R> struct Impl {
           const char* e = getenv("I2C_QUAD_PASSES_MAX_B");
           return e ? atoi(e) : -2;
         }();
-        const int min_b = forced_max > -2 ? 1 : quad_chunk_passes_window<M>::min_b, max_b = forced_max > -2 ? forced_max : quad_chunk_passes_window<M>::max_b;
+        const int min_b = forced_max > -2 ? 1 : quad_chunk_passes_min_b<M>::value, max_b = forced_max > -2 ? forced_max : quad_chunk_passes_max_b<M>::value;
         if ((p->group_lanes == 0 || p->group_lanes == I2C_LANES_QUAD) && p->B >= min_b && p->B <= max_b) return I2C_FAMILY_QUAD;
       }
     }
@@ -1084,7 +967,7 @@ template <class M, typename R, typename S = R> struct Impl {
         return e ? atoi(e) : -2;
       }();
       constexpr long EC = M::NX + M::NX * M::NX + sym(M::NX);
-      const int max_b = forced_max > -2 ? forced_max : quad_chunk_stitch_window<M>::max_b;
+      const int max_b = forced_max > -2 ? forced_max : quad_chunk_stitch_max_b<M>::value;
       return p->inference == I2C_INF_CUBATURE && (p->group_lanes == 0 || p->group_lanes == I2C_LANES_QUAD) && p->B <= max_b && quad_supported(p, c) == I2C_OK &&
              EC * (long)p->B * (long)sizeof(R) < (1L << 31);
     }
@@ -1097,7 +980,7 @@ template <class M, typename R, typename S = R> struct Impl {
       // (unit cubature rule -- a Linearize() graph propagates with it, i2c.py:109-115 --, trajectory-major posterior)
       if (sweep == I2C_SWEEP_PROPAGATE && (p->group_lanes == 0 || p->group_lanes == 64 || p->group_lanes == I2C_LANES_QUAD) &&
           (p->inference == I2C_INF_CUBATURE || p->inference == I2C_INF_LINEARIZE) && p->post_layout == 1 &&
-          ((c.rule_xu.unit && c.rule_xu.w0 == R(0)) || quad_general_exists<M>()) && window_32bit_ok(p) == I2C_OK) {
+          (unit_rule(c.rule_xu) || quad_general_exists<M>()) && window_32bit_ok(p) == I2C_OK) {
         // (the posterior / propagation cells are addressed through 32-bit offsets of one window per cell, masked stores parked at
         //  2 GiB like the other quad forms: beyond it the offsets would wrap silently -- refused here, as group_supported does)
         constexpr long EP = C::E_POST > C::E_PROP ? C::E_POST : C::E_PROP;
@@ -1119,19 +1002,19 @@ template <class M, typename R, typename S = R> struct Impl {
           min_b = M::QUAD_BACKWARD_MIN_B > M::QUAD_FORWARD_MIN_B ? M::QUAD_BACKWARD_MIN_B : M::QUAD_FORWARD_MIN_B;
         } else {
           // d <= 8 (round 6), two forms of backward_quad8_body. (i) The fused walk of four trajectories per wavefront, ONE pass over the
-          // forward messages: on request (group_lanes = 64 with the schedule left open or "fused"), or inside quad_backward_window
+          // forward messages: on request (group_lanes = 64 with the schedule left open or "fused"), or inside quad_backward_min_b .. _max_b
           // (no in-tree model has one). (ii) The WALKER of the chunked schedule (compose / stitch / reduce stay lane kernels): on
-          // request (group_lanes = 64 with "chunked"), or the default inside the model's quad_chunk_walk_window where the chunked
+          // request (group_lanes = 64 with "chunked"), or the default inside the model's quad_chunk_walk_min_b .. _max_b where the chunked
           // schedule is the batch's default (quad_chunk_default). An explicit "two_pass" is the lane kernels'.
           // I2C_LANES_QUAD asks for the quad FORWARD sweep only: its backward sweep resolves as the default does (below).
           asked = p->group_lanes == 64;
           sweep_ok = asked ? p->backward_mode != I2C_BWD_TWO_PASS : p->backward_mode == I2C_BWD_AUTO;
-          min_b = quad_backward_window<M>::min_b, max_b = quad_backward_window<M>::max_b;
-          if (!asked && quad_chunk_default(p)) min_b = quad_chunk_walk_window<M>::min_b, max_b = quad_chunk_walk_window<M>::max_b;
+          min_b = quad_backward_min_b<M>::value, max_b = quad_backward_max_b<M>::value;
+          if (!asked && quad_chunk_default(p)) min_b = quad_chunk_walk_min_b<M>::value, max_b = quad_chunk_walk_max_b<M>::value;
         }
       }
       // (d = 16 with general cubature weights: the wave kernels only have the unit rule -- the quad kernels at every batch size)
-      const bool general_wide = QG<M>::WIDE && quad_general_exists<M>() && (!c.rule_xu.unit || !c.rule_x.unit || c.rule_xu.w0 != R(0) || c.rule_x.w0 != R(0));
+      const bool general_wide = QG<M>::WIDE && quad_general_exists<M>() && !unit_rule(c);
       if (sweep_ok && (asked || (p->group_lanes == 0 && ((p->B >= min_b && p->B <= max_b) || general_wide)))) {
         const int rc = quad_supported(p, c);
         if (rc == I2C_OK) return I2C_FAMILY_QUAD;
@@ -1296,7 +1179,7 @@ template <class M, typename R, typename S = R> struct Impl {
       return (lane_rule == I2C_BWD_TWO_PASS && p->inference == I2C_INF_CUBATURE) ? I2C_BWD_TWO_PASS : I2C_BWD_FUSED;
     if constexpr (HAS_QUAD_BACKWARD && !QG<M>::WIDE && LANE) {
       // d <= 8 quad: the fused walk, or the chunked schedule with the quad walker (compose / stitch / reduce are the lane kernels) --
-      // when asked for by name, or as the model's default inside its quad_chunk_walk_window
+      // when asked for by name, or as the model's default inside its quad_chunk_walk_min_b .. _max_b
       if (fam == I2C_FAMILY_QUAD && p->T >= 8 && (p->backward_mode == I2C_BWD_CHUNKED || quad_chunk_default(p))) return I2C_BWD_CHUNKED;
     }
     if (fam == I2C_FAMILY_QUAD || fam == I2C_FAMILY_GROUP) return I2C_BWD_FUSED;  // four trajectories / a group of lanes walk T-1..0
@@ -1398,12 +1281,7 @@ template <class M, typename R, typename S = R> struct Impl {
         if (M::NZT == 0) return I2C_EINVAL;     // no terminal observation: the reference fails at i2c.py:500-501
         if constexpr (!MIXED) {
           if (pick_mode(p) == I2C_BWD_CHUNKED) {  // (pick_mode: asked for or the default below I2C_BWD_FUSED_MIN_B, with a workspace)
-            ChunkArgs<R, R> ch{a, nullptr, nullptr, nullptr, 0, 0};
-            chunk_geometry(p->B, p->T, &ch.n_chunks, &ch.chunk_len);
-            constexpr int NX = M::NX;
-            ch.comp = (R*)p->work;
-            ch.bnd = ch.comp + (size_t)ch.n_chunks * (NX + NX * NX + sym(NX)) * p->B;
-            ch.part = ch.bnd + (size_t)ch.n_chunks * (NX + sym(NX)) * p->B;
+            const ChunkArgs<R, R> ch = chunk_args<M>(p, a);
             int rc = launch(k_chunk_compose<M, R, R>, p->B, ch.n_chunks, LANE_BLOCK, stream, c, ch);
             if (rc == I2C_OK) rc = launch(k_chunk_stitch_lin<M, R>, p->B, 1, LANE_BLOCK, stream, c, ch);
             if (rc == I2C_OK) rc = launch(k_chunk_walk_lin<M, R>, p->B, ch.n_chunks, LANE_BLOCK, stream, c, ch);
@@ -1417,12 +1295,7 @@ template <class M, typename R, typename S = R> struct Impl {
       if (p->inference == I2C_INF_GAUSS_HERMITE) {  // the fused walk with the grid transform, or (small batches) the chunked form:
         if constexpr (!MIXED) {                     // the composition of the x-marginal recursion has no transform in it
           if (pick_mode(p) == I2C_BWD_CHUNKED) {
-            ChunkArgs<R, R> ch{a, nullptr, nullptr, nullptr, 0, 0};
-            chunk_geometry(p->B, p->T, &ch.n_chunks, &ch.chunk_len);
-            constexpr int NX = M::NX;
-            ch.comp = (R*)p->work;
-            ch.bnd = ch.comp + (size_t)ch.n_chunks * (NX + NX * NX + sym(NX)) * p->B;
-            ch.part = ch.bnd + (size_t)ch.n_chunks * (NX + sym(NX)) * p->B;
+            const ChunkArgs<R, R> ch = chunk_args<M>(p, a);
             C cr = c;  // reduction over chunks instead of cells: same kernel, T := number of chunks
             cr.T = ch.n_chunks;
             CellArgs<R> ared = a;
@@ -1446,12 +1319,7 @@ template <class M, typename R, typename S = R> struct Impl {
   static int backward_chunked(const I2cProblem* p, const C& c, const CellArgs<R, S>& a, const MstepArgs<R>& ms, MstepFuse* fuse, void* stream,
                               const bool quad_walk) {
     if constexpr (LANE) {
-      ChunkArgs<R, S> ch{a, nullptr, nullptr, nullptr, 0, 0};
-      chunk_geometry(p->B, p->T, &ch.n_chunks, &ch.chunk_len);
-      constexpr int NX = M::NX;
-      ch.comp = (R*)p->work;
-      ch.bnd = ch.comp + (size_t)ch.n_chunks * (NX + NX * NX + sym(NX)) * p->B;
-      ch.part = ch.bnd + (size_t)ch.n_chunks * (NX + sym(NX)) * p->B;
+      const ChunkArgs<R, S> ch = chunk_args<M>(p, a);
       C cr = c;  // reduction over chunks instead of cells: same kernel, T := number of chunks
       cr.T = ch.n_chunks;
       CellArgs<R, S> ared = a;
