@@ -152,16 +152,35 @@ def batched_inputs(case, B, seed=1234, x0_scale=1e-2):
     return x0, mu_u
 
 
-def check_batch_against_oracle(name, lib, device, B, n_iters, tol=1e-8, dtype=torch.float64, tol_policy=None, **kw):
-    """Batched engine vs the batched CPU oracle on identical inputs, all trajectories, every cell."""
+def with_horizon(case, T):
+    """The same problem over T cells: meta["T"] replaced and the prior mean of the actions cut, or -- where T exceeds the golden's
+    horizon -- tiled (it is only a prior mean)."""
+    import json
+
+    mu_u = case["mu_u"]
+    mu_u = np.tile(mu_u, (-(-T // mu_u.shape[0]), 1))[:T]
+    return type(case)({**dict(case), "meta": np.array(json.dumps({**case.meta, "T": int(T)})), "mu_u": mu_u})
+
+
+def check_batch_against_oracle(name, lib, device, B, n_iters, tol=1e-8, dtype=torch.float64, tol_policy=None, T=None,
+                               optional_outputs=False, **kw):
+    """Batched engine vs the batched CPU oracle on identical inputs, all trajectories, every cell. T: another horizon than the
+    golden case's (with_horizon). optional_outputs: the engine also writes the smoothed state entering every cell, the observed
+    marginal and the per-cell cost statistics (the walkers' non-lean variants), and those are compared too."""
     g = load_case(name)
+    if T is not None:
+        g = with_horizon(g, T)
     meta_override = kw.pop("meta_override", None)
     if meta_override:  # the same case with other hyper-parameters (e.g. the temperature), for the engine AND the oracle
         import json
 
         g = type(g)({**dict(g), "meta": np.array(json.dumps({**g.meta, **meta_override}))})
     x0, mu_u = batched_inputs(g, B)
+    if optional_outputs:
+        kw = dict(kw, keep_xm=True, keep_zpost=True)
     eng = engine_from_case(g, lib, device, dtype=dtype, x0=x0, mu_u=mu_u, **kw)
+    if optional_outputs:
+        eng.cell_stats = torch.zeros(eng.H, 2, eng.B, dtype=eng.dtype, device=eng.device)
     g2 = dict(g)
     if "quad" in kw:  # the cubature weights asked of the engine: the oracle integrates with the same rule
         import json
@@ -189,5 +208,15 @@ def check_batch_against_oracle(name, lib, device, B, n_iters, tol=1e-8, dtype=to
         close(np_(sigK), o.sigK, tol_policy, f"{name} B={B} it{it} sigK")
         close(np_(eng.alpha), o.alpha, tol, f"{name} B={B} it{it} alpha")
         close(np_(eng.costs_m[-1]), o.costs_m[-1], tol, f"{name} B={B} it{it} cost")
+        if optional_outputs:
+            m3, s3 = eng.smoothed_next_state()
+            close(np_(m3), o.mu_x3_m, tol, f"{name} B={B} it{it} mu_x3_m")
+            close(np_(s3), o.sig_x3_m, tol, f"{name} B={B} it{it} sig_x3_m")
+            mz, sz = eng.observed_marginal()
+            close(np_(mz), o.mu_z0_m, tol, f"{name} B={B} it{it} mu_z0_m")
+            close(np_(sz), o.sig_z0_m, tol, f"{name} B={B} it{it} sig_z0_m")
+            cm, cv = o._gaussian_cost(o.mu_z0_m, o.sig_z0_m)  # (B, T): the cost mean and variance of every cell
+            close(np_(eng.cell_stats[:, 0]).T, cm, tol, f"{name} B={B} it{it} cell cost")
+            close(np_(eng.cell_stats[:, 1]).T, cv, tol, f"{name} B={B} it{it} cell cost variance")
     assert eng.failures() == []
     return eng, o
