@@ -95,8 +95,10 @@ enum {
   I2C_FAMILY_LANE = 1,  /* one trajectory per lane, every block in that lane's registers (d = nx + nu <= 8)              */
   I2C_FAMILY_GROUP = 2, /* G = I2cDims.group_lanes lanes per trajectory, blocks row-distributed, exchanged through LDS  */
   I2C_FAMILY_WAVE = 3,  /* one wavefront per trajectory: 16 x 16 blocks in the MFMA accumulator layout (d = 16)          */
-  I2C_FAMILY_QUAD = 4   /* four trajectories per wavefront: 4 x 4 blocks on v_mfma_f64_4x4x4_4b_f64, one element per lane
+  I2C_FAMILY_QUAD = 4,  /* four trajectories per wavefront: 4 x 4 blocks on v_mfma_f64_4x4x4_4b_f64, one element per lane
                            (forward and backward sweep: every model; propagation and filter step: d = 16)                  */
+  I2C_FAMILY_GRID = 5   /* I2C_INF_GAUSS_HERMITE: one wavefront per trajectory runs the one-lane cell, the gh_degree^d grid points of
+                           every transform strided over its 64 lanes and summed across them (forward, backward, propagate; fp64) */
 };
 /* I2cProblem.group_lanes = I2C_LANES_QUAD asks for the quad kernels of a model that also has wave kernels (64 = the
  * wave kernels there): the 12-state quadrotor -- forward and backward sweep, at any batch size. On a d <= 8 model it asks for the
@@ -201,6 +203,11 @@ typedef struct I2cProblem {
                               CubatureQuadrature(alpha, beta, kappa) -- with general weights the d = 16 model runs on them at every
                               batch size; the closed-loop propagation and the filter step of the d = 16 model run on the quad
                               kernels too: propagate_quad_body, ckf_quad_body)
+                              64 with I2C_INF_GAUSS_HERMITE: the grid kernels (I2C_FAMILY_GRID) of every model that has one-lane
+                              kernels, out-of-tree models included -- forward, backward and propagate sweeps, fp64 storage
+                              (I2C_F64_F32S: I2C_ENOTSUP); the backward sweep has one schedule, the fused walk, without a workspace
+                              (I2C_BWD_CHUNKED / _TWO_PASS requests are answered with it); the buffers are the one-lane kernels'
+                              (post_layout 0), so sweeps of the two families can be mixed; the filter step keeps its cubature rule;
                               I2cDims.group_lanes: run forward / backward / propagate / filter with that many lanes of
                               a wavefront per trajectory (fp64, cubature rule;
                               the backward sweep then has one schedule, the fused walk); -1: one lane per trajectory for

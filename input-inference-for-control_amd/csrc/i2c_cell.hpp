@@ -626,11 +626,51 @@ I2C_FN void grid_transform_ct(const Rule<R>& rule, const R* m, const R* L, const
     for (int l = 0; l <= k; ++l) Sy[tri(k, l)] -= s1[k] * s1[l];
 }
 
-// GRID selects the tensor-grid rule at compile time; the sigma-point kernels are unchanged by it.
-template <bool GRID, class M, class ST, int DIN, int DOUT, bool CROSS, bool UNITW = false, typename R, class F>
+// GRID selects the rule of a cell body at compile time: 0 the sigma points, GRID_LANE the tensor grid walked by the body's own lane,
+// GRID_WAVE the tensor grid strided over the 64 lanes of a wavefront that all run the body on ONE trajectory (the grid family,
+// i2c_grid.hpp). In a GRID_WAVE body every lane holds the same bits in every value -- grid_allreduce guarantees it after a
+// transform, everything else is computed redundantly from the same inputs -- so its control flow is wave-uniform; loads are
+// same-address broadcasts and only lane 0 stores (grid_writer). The sigma-point and GRID_LANE kernels are unchanged by it.
+constexpr int GRID_LANE = 1, GRID_WAVE = 2;
+#ifdef I2C_HOST_SIM
+// The simulated lane of a GRID_WAVE body (tests only): the 64 lanes of a trajectory are 64 cooperatively scheduled contexts of ONE
+// thread (grid_sim_team, i2c_grid.hpp); what the device reads from its lane id and exchanges with cross-lane instructions comes
+// from here. xch: 64 x GridXch<M>::N values.
+struct GridLaneSim {
+  int l;
+  double* xch;
+};
+inline thread_local GridLaneSim grid_lane_sim{0, nullptr};
+inline void grid_sim_sync();  // the team's barrier: every lane arrives before any lane goes on (i2c_grid.hpp)
+#endif
+I2C_FN int grid_lane() {
+#ifdef I2C_HOST_SIM
+  return grid_lane_sim.l;
+#else
+  return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+#endif
+}
+// does this lane store the body's results? (a compile-time `true` in the one-lane kernels)
+template <int GRID> I2C_FN bool grid_writer() {
+  if constexpr (GRID == GRID_WAVE) return grid_lane() == 0;
+  else return true;
+}
+// between a body's read of a location and its writer's update of the same one (the tempering state of covariance control): the
+// device's lanes run in lockstep, the simulation's lanes wait for each other
+template <int GRID> I2C_FN void grid_read_before_write() {
+#ifdef I2C_HOST_SIM
+  if constexpr (GRID == GRID_WAVE) grid_sim_sync();
+#endif
+}
+template <class M, int DIN, int DOUT, bool CROSS, typename R, class F>
+I2C_FN void grid_transform_wave(const Rule<R>& rule, const R* m, const R* L, const F& f, R* my, R* Sy, R* Sxy);  // i2c_grid.hpp
+
+template <int GRID, class M, class ST, int DIN, int DOUT, bool CROSS, bool UNITW = false, typename R, class F>
 I2C_FN void transform(const Rule<R>& rule, const R* m, const R* Sin, const R* L, const F& f, R* my, R* Sy, R* Sxy,
                       const PolyTab<R>* tab = nullptr) {
-  if constexpr (GRID) {
+  if constexpr (GRID == GRID_WAVE) {
+    grid_transform_wave<M, DIN, DOUT, CROSS>(rule, m, L, f, my, Sy, Sxy);
+  } else if constexpr (GRID != 0) {
     if constexpr (DIN <= 3) {  // degrees 2 .. 4 of the pendulum-sized models: the unrolled grid (wave-uniform choice)
       if (rule.gh_degree == 3) return grid_transform_ct<M, 3, DIN, DOUT, CROSS>(rule, m, L, f, my, Sy, Sxy);
       if (rule.gh_degree == 4) return grid_transform_ct<M, 4, DIN, DOUT, CROSS>(rule, m, L, f, my, Sy, Sxy);
@@ -661,7 +701,7 @@ template <typename R, typename S = R> struct FwdArgs {
 // LEAN = the common case fixed at compile time (weights sum to 1, shared target, trajectory-level alpha, no
 // joint-prior output): the corresponding wave-uniform runtime branches disappear from the cell, which keeps
 // it one scheduling region. The generic variant (LEAN = false) handles everything.
-template <class M, typename R, bool LEAN = false, bool GRID = false, typename ST_ = R>
+template <class M, typename R, bool LEAN = false, int GRID = 0, typename ST_ = R>
 I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST_>& a, const int b) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NU = C::NU, NZ = C::NZ, NZT = C::NZT, D = C::D;
@@ -671,6 +711,7 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
   const unsigned bo = (unsigned)b * W;     // the lane's byte offset inside any row
   const unsigned rb0 = (unsigned)(B * W);  // bytes per row (wave-uniform)
   const R alpha_traj = a.alpha[b];
+  const bool wr = grid_writer<GRID>();  // (GRID_WAVE: lane 0 of the trajectory's wavefront; `true` otherwise)
   int fail = 0;  // first failure of this trajectory, (reason << 16) | (t + 1); kept in a register, stored once
 
   R mu_x[NX], sig_x[sym(NX)];
@@ -847,7 +888,7 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
 #pragma unroll
         for (int q = 0; q <= p; ++q) L0[tri(NX + p, NX + q)] = Luu[tri(p, q)];
     }
-    if (!LEAN && a.prior_out) {
+    if (!LEAN && a.prior_out && wr) {
       const Window w = make_window(a.prior_out + (unsigned long)t * (D + sym(D)) * B, (unsigned long)(D + sym(D)) * rb);
 #pragma unroll
       for (int e = 0; e < D; ++e) wst(w, VOFF ? 0u : (e) * rb, VOFF ? voff[e] : bo, (ST_)mu0[e]);
@@ -885,10 +926,12 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
     }
     // mu0 / S0 now hold mu_xu1_f / sig_xu1_f
     const Window out = make_window(a.fwd + (unsigned long)t * C::E_FWD * B, (unsigned long)C::E_FWD * rb);
+    if (wr) {
 #pragma unroll
-    for (int e = 0; e < D; ++e) wst(out, VOFF ? 0u : (e) * rb, VOFF ? voff[e] : bo, (ST_)mu0[e]);
+      for (int e = 0; e < D; ++e) wst(out, VOFF ? 0u : (e) * rb, VOFF ? voff[e] : bo, (ST_)mu0[e]);
 #pragma unroll
-    for (int e = 0; e < sym(D); ++e) wst(out, VOFF ? 0u : (D + e) * rb, VOFF ? voff[D + e] : bo, (ST_)S0[e]);
+      for (int e = 0; e < sym(D); ++e) wst(out, VOFF ? 0u : (D + e) * rb, VOFF ? voff[D + e] : bo, (ST_)S0[e]);
+    }
 
     // ---- 3. dynamics push-through (i2c.py:415-421) and smoother gain (i2c.py:423-425) --
     sched_fence<(D >= 6)>();
@@ -934,8 +977,10 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
     }
     // J is written out BEFORE the terminal update so that its d*nx registers are dead there (with J
     // live the terminal block is the register peak of the large models and spills to scratch)
+    if (wr) {
 #pragma unroll
-    for (int e = 0; e < D * NX; ++e) wst(out, VOFF ? 0u : (D + sym(D) + NX + sym(NX) + e) * rb, VOFF ? voff[D + sym(D) + NX + sym(NX) + e] : bo, (ST_)Sxy[e]);
+      for (int e = 0; e < D * NX; ++e) wst(out, VOFF ? 0u : (D + sym(D) + NX + sym(NX) + e) * rb, VOFF ? voff[D + sym(D) + NX + sym(NX) + e] : bo, (ST_)Sxy[e]);
+    }
     sched_fence<(D >= 6)>();
 
     // ---- 4. terminal cost observation on the flagged cell, after J (i2c.py:430-443) ----
@@ -957,13 +1002,15 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
       for (int i = 0; i < sym(NX); ++i) Lx[i] = L3[i];
     }
     fail = fold_cell_failure(fail, cell_bad, t);
+    if (wr) {
 #pragma unroll
-    for (int e = 0; e < NX; ++e) wst(out, VOFF ? 0u : (D + sym(D) + e) * rb, VOFF ? voff[D + sym(D) + e] : bo, (ST_)mu_x[e]);
+      for (int e = 0; e < NX; ++e) wst(out, VOFF ? 0u : (D + sym(D) + e) * rb, VOFF ? voff[D + sym(D) + e] : bo, (ST_)mu_x[e]);
 #pragma unroll
-    for (int e = 0; e < sym(NX); ++e) wst(out, VOFF ? 0u : (D + sym(D) + NX + e) * rb, VOFF ? voff[D + sym(D) + NX + e] : bo, (ST_)sig_x[e]);
+      for (int e = 0; e < sym(NX); ++e) wst(out, VOFF ? 0u : (D + sym(D) + NX + e) * rb, VOFF ? voff[D + sym(D) + NX + e] : bo, (ST_)sig_x[e]);
+    }
 
   }
-  if (fail != 0 && a.status[b] == 0) a.status[b] = fail;
+  if (wr && fail != 0 && a.status[b] == 0) a.status[b] = fail;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -972,13 +1019,15 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
 
 // End of chain (i2c.py:546-564): the smoothed terminal state, either the filtered one or, for
 // covariance control, its product with the tempered terminal prior (i2c.py:548-559).
-template <class M, typename R>
+template <class M, typename R, int GRID = 0>
 I2C_FN void end_of_chain(const Consts<M, R>& c, R* temp, const int b, const R* m3f, const R* S3f, R* m3m, R* S3m,
                          int32_t* status) {
   constexpr int NX = M::NX;
+  const bool wr = grid_writer<GRID>();
   if (c.has_x_terminal) {
     const R tmp = temp[b];
-    temp[b] = tmp + c.dtemp;
+    grid_read_before_write<GRID>();
+    if (wr) temp[b] = tmp + c.dtemp;
     R St[sym(NX)], Ssum[sym(NX)], rinv[NX];
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) {
@@ -1026,7 +1075,7 @@ I2C_FN void end_of_chain(const Consts<M, R>& c, R* temp, const int b, const R* m
 #pragma unroll
     for (int i = 0; i < NX; ++i) r1[i] += r2[i];
     symv<NX>(S3m, r1, m3m);
-    if (!ok) set_status(status, b, 6, c.T - 1);
+    if (!ok && wr) set_status(status, b, 6, c.T - 1);
   } else {
 #pragma unroll
     for (int i = 0; i < NX; ++i) m3m[i] = m3f[i];
@@ -1090,29 +1139,32 @@ I2C_FN void gaussian_cost(const R* W, const bool w_diag, const R* mz, const R* S
 }
 
 // Terminal observation statistics (i2c.py:567-570, 989-992): tr(Qf (errT errT^T + sig_z3_m)).
-template <class M, typename R, bool GRID = false>
+template <class M, typename R, int GRID = 0>
 I2C_FN R terminal_obs_stats(const Consts<M, R>& c, const int b, const R* m3m, const R* S3m, R* term_stats,
                             int32_t* status) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NZT = C::NZT;
   const long B = c.B;
+  const bool wr = grid_writer<GRID>();
   R trT = R(0);
   if (NZT > 0 && c.has_Qf) {
     constexpr int NT = C::NZT1;
     R L3[sym(NX)], rinv3[NX], mzt[NT], Szt[sym(NT)];
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) L3[i] = S3m[i];
-    if (!chol<NX>(L3, rinv3)) set_status(status, b, 6, c.T - 1);
+    if (!chol<NX>(L3, rinv3) && wr) set_status(status, b, 6, c.T - 1);
     transform<GRID, M, TermStruct<M>, NX, NT, false>(c.rule_x, m3m, S3m, L3, ObserveTermF<M, R>{params_of(c, b)}, mzt, Szt,
                                                   (R*)nullptr);
     R tv;
     gaussian_cost<NT>(c.Qf, c.qf_diag != 0, mzt, Szt, c.zg_term, &trT, &tv);
+    if (wr) {
 #pragma unroll
-    for (int k = 0; k < NT; ++k) term_stats[(long)(3 + k) * B + b] = mzt[k];
+      for (int k = 0; k < NT; ++k) term_stats[(long)(3 + k) * B + b] = mzt[k];
 #pragma unroll
-    for (int k = 0; k < sym(NT); ++k) term_stats[(long)(3 + NT + k) * B + b] = Szt[k];
+      for (int k = 0; k < sym(NT); ++k) term_stats[(long)(3 + NT + k) * B + b] = Szt[k];
+    }
   }
-  term_stats[b] = trT;
+  if (wr) term_stats[b] = trT;
   return trT;
 }
 
@@ -1122,7 +1174,7 @@ I2C_FN R terminal_obs_stats(const Consts<M, R>& c, const int b, const R* m3m, co
 //   K L_xx = L_ux  ->  K^T = L_xx^{-T} L_ux^T ;  sigK = L_uu L_uu^T ;  k = mu_u - K mu_x.
 // In: mu/S = mu_xu1_f / sig_xu1_f, J, dm = mu_x3_m - mu_x3_f, dS = sig_x3_m - sig_x3_f.
 // Out: mu/S = mu_xu0_m / sig_xu0_m, ctl = [K | k | sigK], mz/Sz, cost mean / variance.
-template <class M, typename R, bool GRID = false>
+template <class M, typename R, int GRID = 0>
 I2C_FN bool cell_posterior(const Consts<M, R>& c, const int b, const R* zt, R* mu, R* S, const R* J, const R* dm, const R* dS,
                            R* ctl, R* mz, R* Sz, R* cm, R* cv, const PolyTab<R>* tab = nullptr) {
   using C = Consts<M, R>;
@@ -1377,7 +1429,7 @@ I2C_FN void reduce_partial(const Consts<M, R>& c, const R* cell_stats, const int
 // moves E_FWD + E_POST elements per cell instead of the two-pass form's ~2x that.
 // ------------------------------------------------------------------------------------------
 // LEANW: as in chunk_walk_body (no optional outputs, one shared target: a compile-time count of the memory operations of a cell).
-template <class M, typename R, bool GRID = false, typename S_ = R, bool LEANW = false>
+template <class M, typename R, int GRID = 0, typename S_ = R, bool LEANW = false>
 I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, S_>& a_in, const int b) {
   CellArgs<R, S_> a = a_in;
   if (LEANW) a.xm = nullptr, a.zpost = nullptr, a.cell_stats = nullptr;
@@ -1389,6 +1441,7 @@ I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, 
   const unsigned long B = c.B;
   const int T = c.T;
   const unsigned bo = (unsigned)b * W, rb = (unsigned)(B * W);
+  const bool wr = grid_writer<GRID>();  // (GRID_WAVE: lane 0 of the trajectory's wavefront; `true` otherwise)
 
   constexpr bool DOUBLE_BUFFER = C::D <= 5;  // see chunk_walk_body
   constexpr bool VOFF = LEANW && !GRID && C::D <= 5;  // row offsets in VGPRs, sincos table in registers (chunk_walk_body)
@@ -1412,7 +1465,7 @@ I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, 
 #pragma unroll
         for (int e = 0; e < C::E_FWD; ++e) row[e] = opaque(row[e]);
       }
-      end_of_chain<M, R>(c, a.temp, b, row + O_MU3, row + O_S3, m3m, S3m, a.status);
+      end_of_chain<M, R, GRID>(c, a.temp, b, row + O_MU3, row + O_S3, m3m, S3m, a.status);
     } else {
       // Only the filtered terminal state here: the loop below loads EVERY cell's row at the top of its own cell, the last
       // one included. Loaded here and skipped there, the row becomes a loop-carried value and all 100+ doubles of it stay
@@ -1422,7 +1475,7 @@ I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, 
       for (int e = 0; e < NX; ++e) m3f[e] = (R)wld<S_>(w, (O_MU3 + e) * rb, bo);
 #pragma unroll
       for (int e = 0; e < sym(NX); ++e) S3f[e] = (R)wld<S_>(w, (O_S3 + e) * rb, bo);
-      end_of_chain<M, R>(c, a.temp, b, m3f, S3f, m3m, S3m, a.status);
+      end_of_chain<M, R, GRID>(c, a.temp, b, m3f, S3f, m3m, S3m, a.status);
     }
   }
   terminal_obs_stats<M, R, GRID>(c, b, m3m, S3m, a.term_stats, a.status);
@@ -1439,7 +1492,7 @@ I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, 
 #pragma unroll
       for (int e = 0; e < C::E_FWD; ++e) row[e] = (R)wld<S_>(w, e * rb, bo);
     }
-    if (a.xm) {
+    if (a.xm && wr) {
       S_* xo = const_cast<S_*>(a.xm) + ((long)t * C::E_XM) * B + b;
 #pragma unroll
       for (int i = 0; i < NX; ++i) xo[(long)i * B] = (S_)m3m[i];
@@ -1456,8 +1509,8 @@ I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, 
     R* mu = row;
     R* S = row + D;
     R ctl[C::E_POST - D - sym(D)], mz[NZ], Sz[sym(NZ)], cm, cv;
-    if (!cell_posterior<M, R, GRID>(c, b, zt, mu, S, row + O_J, dm, dS, ctl, mz, Sz, &cm, &cv, tab)) set_status(a.status, b, 7, t);
-    store_cell<M, R, S_>(c, a, t, b, mu, S, ctl, mz, Sz, cm, cv, VOFF ? voff : nullptr);
+    if (!cell_posterior<M, R, GRID>(c, b, zt, mu, S, row + O_J, dm, dS, ctl, mz, Sz, &cm, &cv, tab) && wr) set_status(a.status, b, 7, t);
+    if (wr) store_cell<M, R, S_>(c, a, t, b, mu, S, ctl, mz, Sz, cm, cv, VOFF ? voff : nullptr);
     sum_m += cm;
     sum_v += cv;
 #pragma unroll
@@ -1469,8 +1522,10 @@ I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, 
       for (int e = 0; e < C::E_FWD; ++e) row[e] = nxt[DOUBLE_BUFFER ? e : 0];
     }
   }
-  a.term_stats[B + b] = sum_m;
-  a.term_stats[2 * B + b] = sum_v;
+  if (wr) {
+    a.term_stats[B + b] = sum_m;
+    a.term_stats[2 * B + b] = sum_v;
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1568,7 +1623,7 @@ I2C_HD inline void chunk_compose_body(const Consts<M, R>& c, const ChunkArgs<R, 
   for (int i = 0; i < sym(NX); ++i) out[(long)(NX + NX * NX + i) * B] = Cc[i];
 }
 
-template <class M, typename R, typename S_ = R, bool GRID = false>
+template <class M, typename R, typename S_ = R, int GRID = 0>
 I2C_HD inline void chunk_stitch_body(const Consts<M, R>& c, const ChunkArgs<R, S_>& a, const int b) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, D = C::D;
@@ -1627,7 +1682,7 @@ I2C_HD inline void chunk_stitch_body(const Consts<M, R>& c, const ChunkArgs<R, S
 // its use, so its s_waitcnt at the top of a cell also waits for the PREVIOUS cell's stores to be acknowledged (vmcnt is one
 // in-order counter) -- 41 % of the walk's cycles (profiles/r3_pendulum_B4096_chunked_sq_summary.txt).
 // GRID: the Gauss-Hermite tensor-grid transform in the cell (GaussHermiteQuadrature: the chunked schedule of that rule)
-template <class M, typename R, typename S_ = R, bool LEANW = false, bool GRID = false>
+template <class M, typename R, typename S_ = R, bool LEANW = false, int GRID = 0>
 I2C_HD inline void chunk_walk_body(const Consts<M, R>& c, const ChunkArgs<R, S_>& a, const int ch, const int b) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NZ = C::NZ, D = C::D;
@@ -1783,12 +1838,13 @@ template <typename R> struct PropArgs {
   const uint8_t* expert;  // [T] ring or null: per-cell use_expert_controller (i2c.py:143,160); null: Consts::use_expert
 };
 
-template <class M, typename R, bool GRID = false>
+template <class M, typename R, int GRID = 0>
 I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, const int b) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NU = C::NU, NZ = C::NZ, D = C::D;
   const long B = c.B;
   const int T = c.T;
+  const bool wr = grid_writer<GRID>();  // (GRID_WAVE: lane 0 of the trajectory's wavefront; `true` otherwise)
   R mu_x[NX], sig_x[sym(NX)];
 #pragma unroll
   for (int i = 0; i < NX; ++i) mu_x[i] = a.x0[i * B + b];
@@ -1887,15 +1943,17 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
       joint_from_gain<NX, NU>(mu_x, sig_x, Kt, qmu, qmu + NX, sig_u, mu0, S0);
     }
     R* out = a.prop + ((long)t * C::E_PROP) * B + b;
+    if (wr) {
 #pragma unroll
-    for (int e = 0; e < D; ++e) out[(long)e * B] = mu0[e];
+      for (int e = 0; e < D; ++e) out[(long)e * B] = mu0[e];
 #pragma unroll
-    for (int e = 0; e < sym(D); ++e) out[(long)(D + e) * B] = S0[e];
+      for (int e = 0; e < sym(D); ++e) out[(long)(D + e) * B] = S0[e];
+    }
 
     R L0[sym(D)], rinv[D];
 #pragma unroll
     for (int e = 0; e < sym(D); ++e) L0[e] = S0[e];
-    if (!chol<D>(L0, rinv)) set_status(a.status, b, 8, t);
+    if (!chol<D>(L0, rinv) && wr) set_status(a.status, b, 8, t);
     R zt[NZ], mz[NZ], Sz[sym(NZ)];
 #pragma unroll
     for (int k = 0; k < NZ; ++k) zt[k] = ZPRE ? zt_cur[ZPRE ? k : 0] : (c.z_per_cell ? a.z[((long)c.row(t) * NZ + k) * B + b] : c.zg[k]);
@@ -1908,10 +1966,12 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
     transform<GRID, M, DenseStruct<D>, D, NX, false>(c.rule_xu, mu0, S0, L0, DynamicsF<M, R>{params_of(c, b)}, mu_x, sig_x, (R*)nullptr);
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) sig_x[i] += c.sig_eta_w[i];
+    if (wr) {
 #pragma unroll
-    for (int e = 0; e < NX; ++e) out[(long)(D + sym(D) + e) * B] = mu_x[e];
+      for (int e = 0; e < NX; ++e) out[(long)(D + sym(D) + e) * B] = mu_x[e];
 #pragma unroll
-    for (int e = 0; e < sym(NX); ++e) out[(long)(D + sym(D) + NX + e) * B] = sig_x[e];
+      for (int e = 0; e < sym(NX); ++e) out[(long)(D + sym(D) + NX + e) * B] = sig_x[e];
+    }
     if (ZPRE) {
 #pragma unroll
       for (int k = 0; k < NZ; ++k) zt_cur[k] = zt_nxt[ZPRE ? k : 0];
@@ -1921,8 +1981,10 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
       for (int e = 0; e < C::E_PRI; ++e) pri[e] = nxt[PREFETCH ? e : 0];
     }
   }
-  a.prop_stats[b] = sum_m;
-  a.prop_stats[B + b] = sum_v;
+  if (wr) {
+    a.prop_stats[b] = sum_m;
+    a.prop_stats[B + b] = sum_v;
+  }
   // KL(x3_pf[T-1] || terminal prior) of covariance control (I2cGraph._maximize, i2c.py:1012-1019, mvn_kl_divergence
   // :1223-1229) from the two Cholesky factors: log det ratio = 2 sum log(L2_ii / L1_ii), tr(S2^-1 S1) = ||L2^-1 L1||_F^2.
   R kl = R(0);
@@ -1934,7 +1996,7 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
       L2[i] = c.sig_x_term[i];
     }
     const bool ok = chol<NX>(L1, r1) && chol<NX>(L2, r2);
-    if (!ok) set_status(a.status, b, 8, T - 1);
+    if (!ok && wr) set_status(a.status, b, 8, T - 1);
     R logdet = R(0), tr = R(0), dq[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
@@ -1956,7 +2018,7 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
     for (int i = 0; i < NX; ++i) maha += dq[i] * dq[i];
     kl = R(0.5) * (R(2) * logdet + tr + maha - R(NX));
   }
-  a.prop_stats[2 * B + b] = kl;
+  if (wr) a.prop_stats[2 * B + b] = kl;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -10,7 +10,7 @@
 //
 // Layout: the launch layer of the one-lane kernels (launch(), I2C_KERNEL) and those kernels; the launch layer of the multi-lane
 // kernels (host simulation: sim_teams(); device: I2C_QUAD_SETUP / launch_quad(), the XCD placement) and the group, wave and quad
-// kernels, each with its launcher; the problem constants, the chunk workspace and the per-model batch sizes; Impl<M, R, S>: which
+// kernels, each with its launcher, and the launcher of the grid kernels; the problem constants, the chunk workspace and the per-model batch sizes; Impl<M, R, S>: which
 // family and schedule serve a call, and the entry points.
 #pragma once
 #include "i2c_entry.hpp"
@@ -18,6 +18,7 @@
 #include "i2c_group.hpp"
 #include "i2c_wave.hpp"
 #include "i2c_quad.hpp"
+#include "i2c_grid.hpp"
 #include "i2c_linearize.hpp"
 
 #include <cmath>
@@ -685,6 +686,25 @@ static int launch_quad_ckf(const Consts<M, R>& c, const ZetaArg<M, R>& zeta, con
 #endif
 }
 
+// ---- grid kernels (i2c_grid.hpp): one wavefront per trajectory runs the one-lane body, the Gauss-Hermite grid strided over its lanes ----
+// Device: GRID_WAVES_PER_BLOCK trajectories per workgroup. Host simulation: grid_sim_team() runs the 64 lanes of a trajectory (no
+// threads: see i2c_grid.hpp), one trajectory after the other.
+template <int KIND, class M, typename R, class A>
+static int launch_grid(const Consts<M, R>& c, const A& a, void* stream) {
+#ifdef I2C_HOST_SIM
+  std::unique_ptr<char[]> stacks(new char[64 * GridFibres::STACK]);
+  std::vector<double> xch((size_t)64 * GridXch<M>::N);
+  for (int b = 0; b < c.B; ++b) grid_sim_team(stacks.get(), xch.data(), [&] { grid_body<KIND, M, R>(c, a, b); });
+  return I2C_OK;
+#else
+  const dim3 grid((unsigned)(((long)c.B + GRID_WAVES_PER_BLOCK - 1) / GRID_WAVES_PER_BLOCK)), block(64 * GRID_WAVES_PER_BLOCK);
+  if constexpr (KIND == GRK_FORWARD) hipLaunchKernelGGL((k_grid_forward<M, R>), grid, block, 0, (hipStream_t)stream, c, a);
+  if constexpr (KIND == GRK_BACKWARD) hipLaunchKernelGGL((k_grid_backward<M, R>), grid, block, 0, (hipStream_t)stream, c, a);
+  if constexpr (KIND == GRK_PROPAGATE) hipLaunchKernelGGL((k_grid_propagate<M, R>), grid, block, 0, (hipStream_t)stream, c, a);
+  return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
+#endif
+}
+
 template <int KIND, class M, typename R, typename S, class A>
 static int launch_wave(const Consts<M, R>& c, const A& a, void* stream) {
   if constexpr (KIND == WK_FORWARD) {  // batches whose waves share a SIMD: the variant with the pivot blocks through LDS
@@ -854,7 +874,8 @@ I2C_MODEL_CONST(quad_chunk_stitch_max_b, QUAD_CHUNK_STITCH_MAX_B, -1)
 //                 backward sweeps wherever they apply (Impl::wave_supported); I2cProblem.group_lanes = 64 asks for them
 //   M::GROUP_ONLY the one-lane-per-trajectory kernels are NOT compiled for this model (d = nx + nu > 8 does not fit one
 //                 lane's registers): every call runs the wave or the group kernels
-//   I2cProblem.group_lanes   0: the model's default (Impl::family); G = M::GROUP: ask for the group kernels; 64: the wave kernels;
+//   I2cProblem.group_lanes   0: the model's default (Impl::family); G = M::GROUP: ask for the group kernels; 64: the wave kernels
+//                 (with I2C_INF_GAUSS_HERMITE: the grid kernels, i2c_grid.hpp -- every model with one-lane kernels, fp64);
 //                 -1: one lane per trajectory; anything else: I2C_ENOTSUP
 //   S             storage type of the per-cell buffers: R, or float with R = double (I2C_F64_F32S: the cubature EM path of the
 //                 one-lane, the quad and the wave kernels -- forward, backward, M-step, i2c_learn; everything else is I2C_ENOTSUP)
@@ -867,6 +888,7 @@ template <class M, typename R, typename S = R> struct Impl {
   static constexpr bool HAS_WAVE = M::WAVE && sizeof(R) == 8;  // fp64 matrix instruction; the storage type S may be float
   static constexpr bool HAS_QUAD = M::QUAD && sizeof(R) == 8;  // fp64 matrix instruction (i2c_quad.hpp): forward sweep; the storage type S may be float
   static constexpr bool HAS_QUAD_BACKWARD = HAS_QUAD && quad_backward_exists<M>();  // ... and, for d = 16, the backward sweep
+  static constexpr bool HAS_GRID = LANE && sizeof(R) == 8 && !MIXED;  // the grid kernels run the one-lane bodies: wherever those exist, fp64
 
   // 1: group kernels, 0: one lane per trajectory, < 0: error code
   static int use_group(const I2cProblem* p) {
@@ -976,6 +998,11 @@ template <class M, typename R, typename S = R> struct Impl {
   static constexpr bool HAS_QUAD_CKF = HAS_QUAD && !MIXED && quad_ckf_exists<M>();  // the filter step of the d = 16 form
   static constexpr bool HAS_QUAD_PROP = HAS_QUAD && !MIXED && quad_propagate_exists<M>();  // the closed-loop propagation of the d = 16 form
   static int family(const I2cProblem* p, const C& c, const int sweep) {
+    if constexpr (HAS_GRID) {  // the Gauss-Hermite rule on a wavefront per trajectory: on request only (group_lanes = 64)
+      if (p->group_lanes == 64 && p->inference == I2C_INF_GAUSS_HERMITE &&
+          (sweep == I2C_SWEEP_FORWARD || sweep == I2C_SWEEP_BACKWARD || sweep == I2C_SWEEP_PROPAGATE))
+        return I2C_FAMILY_GRID;
+    }
     if constexpr (HAS_QUAD_PROP) {  // the closed-loop propagation of a matrix-instruction graph: the quad form where it applies
       // (unit cubature rule -- a Linearize() graph propagates with it, i2c.py:109-115 --, trajectory-major posterior)
       if (sweep == I2C_SWEEP_PROPAGATE && (p->group_lanes == 0 || p->group_lanes == 64 || p->group_lanes == I2C_LANES_QUAD) &&
@@ -1135,6 +1162,9 @@ template <class M, typename R, typename S = R> struct Impl {
     if (fam == I2C_FAMILY_GROUP) {
       if constexpr (HAS_GROUP) return launch_group<GK_FORWARD, M, R, G>(c, nullptr, a, stream);
     }
+    if (fam == I2C_FAMILY_GRID) {
+      if constexpr (HAS_GRID) return launch_grid<GRK_FORWARD, M, R>(c, a, stream);
+    }
     if constexpr (LANE) {
       if (p->inference == I2C_INF_LINEARIZE) return launch(k_forward_lin<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
       if (p->inference == I2C_INF_GAUSS_HERMITE)
@@ -1182,7 +1212,7 @@ template <class M, typename R, typename S = R> struct Impl {
       // when asked for by name, or as the model's default inside its quad_chunk_walk_min_b .. _max_b
       if (fam == I2C_FAMILY_QUAD && p->T >= 8 && (p->backward_mode == I2C_BWD_CHUNKED || quad_chunk_default(p))) return I2C_BWD_CHUNKED;
     }
-    if (fam == I2C_FAMILY_QUAD || fam == I2C_FAMILY_GROUP) return I2C_BWD_FUSED;  // four trajectories / a group of lanes walk T-1..0
+    if (fam == I2C_FAMILY_QUAD || fam == I2C_FAMILY_GROUP || fam == I2C_FAMILY_GRID) return I2C_BWD_FUSED;  // four trajectories / a group of lanes / a wavefront walk T-1..0
     if (!LANE) return I2C_ENOTSUP;
     if (p->inference == I2C_INF_LINEARIZE) {
       if (M::NZT == 0) return I2C_EINVAL;  // no terminal observation: the reference fails at i2c.py:500-501
@@ -1275,6 +1305,9 @@ template <class M, typename R, typename S = R> struct Impl {
     }
     if (fam == I2C_FAMILY_GROUP) {  // one schedule: the group walks T-1..0 (the fused form); backward_mode is ignored
       if constexpr (HAS_GROUP) return launch_group<GK_BACKWARD, M, R, G>(c, nullptr, a, stream);
+    }
+    if (fam == I2C_FAMILY_GRID) {  // one schedule as well: the fused walk, no workspace
+      if constexpr (HAS_GRID) return launch_grid<GRK_BACKWARD, M, R>(c, a, stream);
     }
     if constexpr (LANE) {
       if (p->inference == I2C_INF_LINEARIZE) {  // a lane per trajectory walks T-1..0, or (small batches) the chunked form
@@ -1588,6 +1621,9 @@ template <class M, typename R, typename S = R> struct Impl {
     }
     if (fam == I2C_FAMILY_GROUP) {
       if constexpr (HAS_GROUP) return launch_group<GK_PROPAGATE, M, R, G>(c, nullptr, a, stream);
+    }
+    if (fam == I2C_FAMILY_GRID) {
+      if constexpr (HAS_GRID) return launch_grid<GRK_PROPAGATE, M, R>(c, a, stream);
     }
     if constexpr (LANE) {
       if (p->inference == I2C_INF_GAUSS_HERMITE) return launch(k_propagate<M, R, true>, p->B, 1, LANE_BLOCK, stream, c, a);

@@ -118,7 +118,10 @@ class BatchedI2c:
         self.group_lanes = int(group_lanes or 0)
         # 64 = the wave kernels (csrc/i2c_wave.hpp: one wavefront per trajectory, blocks in the fp64 matrix-instruction layout),
         # for the models that have them (dims.wave): forward and backward sweeps; propagation and filter run the model's default
-        ok = self.group_lanes in (0, dims.group_lanes) or (self.group_lanes == -1 and not dims.group_only) or \
+        # 64 with inference="gauss_hermite": the grid kernels (csrc/i2c_grid.hpp: one wavefront per trajectory, the tensor grid strided
+        # over its lanes) of every model that has one-lane kernels; they read and write the one-lane kernels' buffers
+        self.grid_requested = bool(self.group_lanes == 64 and inference == "gauss_hermite" and not dims.group_only)
+        ok = self.group_lanes in (0, dims.group_lanes) or (self.group_lanes == -1 and not dims.group_only) or self.grid_requested or \
             (self.group_lanes == 64 and (dims.wave or dims.quad)) or (self.group_lanes == _native.LANES_QUAD and dims.quad)
         if not ok:
             raise ValueError(f"group_lanes={self.group_lanes}: this model's group kernels use {dims.group_lanes} lanes"
@@ -128,8 +131,10 @@ class BatchedI2c:
         # 64 on a model with the quad kernel (csrc/i2c_quad.hpp: four trajectories per wavefront on the 4 x 4 x 4 fp64 matrix
         # instruction): the FORWARD sweep runs on it, every other sweep on the model's default kernels
         # (_native.LANES_QUAD asks for it on a model that also has wave kernels, where 64 means those)
-        self.quad_requested = bool((self.group_lanes == 64 and dims.quad and not dims.wave) or self.group_lanes == _native.LANES_QUAD)
-        self.uses_group_kernels = bool((self.group_lanes > 0 and not self.quad_requested) or dims.group_only)  # a multi-lane family (group or wave) serves the sweeps
+        self.quad_requested = bool(((self.group_lanes == 64 and dims.quad and not dims.wave) or self.group_lanes == _native.LANES_QUAD)
+                                   and not self.grid_requested)
+        self.uses_group_kernels = bool((self.group_lanes > 0 and not self.quad_requested and not self.grid_requested)
+                                       or dims.group_only)  # a multi-lane family (group or wave) serves the sweeps
         if self.mixed and inference != "cubature":
             raise ValueError("fp32 storage (storage_dtype) is available for the cubature path only")
         if self.mixed and self.uses_group_kernels and not (dims.wave and self.group_lanes in (0, 64, _native.LANES_QUAD)):
@@ -407,7 +412,7 @@ class BatchedI2c:
             self._params_b.copy_(v)
 
     def kernel_family(self, sweep="forward"):
-        """Which kernel family serves a sweep of THIS problem ("lane", "group", "wave" or "quad"): i2c_kernel_family(), the library's
+        """Which kernel family serves a sweep of THIS problem ("lane", "group", "wave", "quad" or "grid"): i2c_kernel_family(), the library's
         single resolver of group_lanes, model defaults and batch thresholds. The last bits of a result depend on it.
         "chunk_passes": the compose + stitch passes of the chunked backward schedule, "chunk_stitch": its stitch pass alone (refused
         when another schedule runs)."""
