@@ -868,17 +868,32 @@ I2C_MODEL_CONST(quad_chunk_stitch_max_b, QUAD_CHUNK_STITCH_MAX_B, -1)
 #undef I2C_MODEL_CONST
 
 // ---- per-(model, dtype) entry points ------------------------------------------------------
-// Which kernels serve a call:
+// Which kernels a model has (i2c_models.hpp):
 //   M::GROUP      lanes per trajectory of the model's group kernels (0: none compiled); fp64 only
-//   M::WAVE       the wave kernels (i2c_wave.hpp: one wavefront per trajectory) exist for this model: its default for the forward and
-//                 backward sweeps wherever they apply (Impl::wave_supported); I2cProblem.group_lanes = 64 asks for them
+//   M::WAVE       the wave kernels (i2c_wave.hpp: one wavefront per trajectory, d = 16) exist for this model
+//   M::QUAD       the quad kernels (i2c_quad.hpp: four trajectories per wavefront) exist for this model
 //   M::GROUP_ONLY the one-lane-per-trajectory kernels are NOT compiled for this model (d = nx + nu > 8 does not fit one
-//                 lane's registers): every call runs the wave or the group kernels
-//   I2cProblem.group_lanes   0: the model's default (Impl::family); G = M::GROUP: ask for the group kernels; 64: the wave kernels
-//                 (with I2C_INF_GAUSS_HERMITE: the grid kernels, i2c_grid.hpp -- every model with one-lane kernels, fp64);
-//                 -1: one lane per trajectory; anything else: I2C_ENOTSUP
+//                 lane's registers): every call runs the wave, quad or group kernels
 //   S             storage type of the per-cell buffers: R, or float with R = double (I2C_F64_F32S: the cubature EM path of the
 //                 one-lane, the quad and the wave kernels -- forward, backward, M-step, i2c_learn; everything else is I2C_ENOTSUP)
+// Which of them serve a problem is decided ONCE per library call: Impl::resolve(problem) -> Plan. It reads I2cProblem.group_lanes
+// (0: the model's default; -1: one lane per trajectory; G = M::GROUP: the group kernels; 64: the wave kernels, the quad kernels of a
+// model without them, the grid kernels under I2C_INF_GAUSS_HERMITE; I2C_LANES_QUAD; anything else: I2C_ENOTSUP) as a Request, then
+// walks one ordered rule list per sweep (forward_family, backward_family, propagate_family, filter_family), then the backward schedule
+// and the passes of the chunked one. The two exports report from the plan (family_of, plan); the launchers (run_forward, run_backward,
+// backward_chunked, run_propagate, run_ckf) read the plan and the presence of optional buffers, never the request fields.
+
+// What a problem resolves to: families are I2C_FAMILY_* or the negative error code the sweep returns
+struct Plan {
+  int forward, backward, propagate, filter;
+  int schedule;   // I2C_BWD_* as i2c_backward_schedule reports it: the workspace of a chunked answer is assumed (Impl::schedule_with)
+  int walker;     // schedule == I2C_BWD_CHUNKED: the family of the walk pass (lane or quad)
+  int compose, stitch;  // ... and of the compose and stitch passes, as I2C_SWEEP_CHUNK_PASSES / _STITCH report them (sigma-point rule only)
+  int rule;       // the rule variant of the lane bodies: I2C_INF_CUBATURE, _LINEARIZE or _GAUSS_HERMITE
+  bool fwd_tm;    // the quad forward sweep writes its messages where a wave / quad backward sweep reads them (Consts::fwd_tm)
+  bool fusable;   // i2c_learn_propagate: a forward sweep and the previous propagation may share a launch (k_forward_propagate)
+};
+
 template <class M, typename R, typename S = R> struct Impl {
   using C = Consts<M, R>;
   static constexpr bool MIXED = sizeof(S) != sizeof(R);
@@ -887,25 +902,42 @@ template <class M, typename R, typename S = R> struct Impl {
   static constexpr bool LANE = !M::GROUP_ONLY;  // one-lane-per-trajectory kernels exist
   static constexpr bool HAS_WAVE = M::WAVE && sizeof(R) == 8;  // fp64 matrix instruction; the storage type S may be float
   static constexpr bool HAS_QUAD = M::QUAD && sizeof(R) == 8;  // fp64 matrix instruction (i2c_quad.hpp): forward sweep; the storage type S may be float
-  static constexpr bool HAS_QUAD_BACKWARD = HAS_QUAD && quad_backward_exists<M>();  // ... and, for d = 16, the backward sweep
+  static constexpr bool WIDE = QG<M>::WIDE;                    // the d = 16 form of the quad kernels
+  static constexpr bool HAS_QUAD_BACKWARD = HAS_QUAD && quad_backward_exists<M>();  // ... and the backward sweep
+  static constexpr bool QUAD8 = HAS_QUAD_BACKWARD && !WIDE && LANE;  // d <= 8: the fused quad walk, and the quad passes of the chunked schedule
+  static constexpr bool HAS_QUAD_CKF = HAS_QUAD && !MIXED && quad_ckf_exists<M>();  // the filter step of the d = 16 form
+  static constexpr bool HAS_QUAD_PROP = HAS_QUAD && !MIXED && quad_propagate_exists<M>();  // the closed-loop propagation of the d = 16 form
   static constexpr bool HAS_GRID = LANE && sizeof(R) == 8 && !MIXED;  // the grid kernels run the one-lane bodies: wherever those exist, fp64
 
-  // 1: group kernels, 0: one lane per trajectory, < 0: error code
-  static int use_group(const I2cProblem* p) {
-    if (p->group_lanes == 0 || (p->group_lanes == 64 && (M::WAVE || M::QUAD)) || (p->group_lanes == I2C_LANES_QUAD && M::QUAD))  // the wave / quad kernels; their missing sweeps run the default
-      return M::GROUP_ONLY ? (HAS_GROUP ? 1 : I2C_ENOTSUP) : 0;
-    if (p->group_lanes == -1) return M::GROUP_ONLY ? I2C_ENOTSUP : 0;  // one lane per trajectory, no hybrid forward
-    return (HAS_GROUP && p->group_lanes == G) ? 1 : I2C_ENOTSUP;
+  // ---- the resolver -------------------------------------------------------------------------------------------------------------
+  // I2cProblem.group_lanes, normalised once against what the model has; nothing below reads the field again
+  enum Request {
+    REQ_DEFAULT,       // 0 (and 64 / I2C_LANES_QUAD where the kernels they name need fp64 arithmetic and R is float)
+    REQ_ONE_LANE,      // -1: one lane per trajectory, no hybrid forward
+    REQ_GROUP,         // G
+    REQ_WAVE,          // 64 on a model with wave kernels (M::WAVE implies d = 16: i2c_wave.hpp)
+    REQ_QUAD,          // 64 on a model with quad kernels only, I2C_LANES_QUAD on a d = 16 model: every sweep the quad form has
+    REQ_QUAD_FORWARD,  // I2C_LANES_QUAD on a d <= 8 model: the quad forward sweep; the other sweeps resolve as the default does
+    REQ_GRID,          // 64 under I2C_INF_GAUSS_HERMITE: forward, backward, propagation on the grid kernels
+    REQ_NOT_OURS       // a width this model does not have
+  };
+  static Request request(const int lanes, const int inference) {
+    if (lanes == 0) return REQ_DEFAULT;
+    if (lanes == -1) return REQ_ONE_LANE;
+    if (lanes == 64 && HAS_GRID && inference == I2C_INF_GAUSS_HERMITE) return REQ_GRID;
+    if (lanes == 64 && (M::WAVE || M::QUAD)) return HAS_WAVE ? REQ_WAVE : (HAS_QUAD ? REQ_QUAD : REQ_DEFAULT);
+    if (lanes == I2C_LANES_QUAD) return HAS_QUAD ? (WIDE ? REQ_QUAD : REQ_QUAD_FORWARD) : REQ_DEFAULT;
+    return (HAS_GROUP && lanes == G) ? REQ_GROUP : REQ_NOT_OURS;
   }
-  // what the group form does not cover: other inference rules; per-cell blocks beyond the 2 GiB the predicated stores of
-  // GIO::st_if park their masked-off lanes behind (the parked offset must stay out of the buffer window)
-  // (closed-loop propagation under Linearize() IS the unit cubature rule: i2c.py:109-115)
-  static int group_supported(const I2cProblem* p, const C&, const int sweep) {
-    if (p->inference != I2C_INF_CUBATURE && !(p->inference == I2C_INF_LINEARIZE && sweep == I2C_SWEEP_PROPAGATE)) return I2C_ENOTSUP;
-    constexpr long EMAX = C::E_FWD > C::E_POST ? (C::E_FWD > C::E_PROP ? C::E_FWD : C::E_PROP) : (C::E_POST > C::E_PROP ? C::E_POST : C::E_PROP);
-    if (EMAX * (long)p->B * (long)sizeof(R) >= (1L << 31)) return I2C_EINVAL;
-    return window_32bit_ok(p);
+  // the requests under which the sweeps that only have a one-lane form run (the Riccati messages): everything but a width the model
+  // has group kernels for or does not have at all (I2C_LANES_QUAD names nothing on a model without quad kernels)
+  static bool lane_request(const int lanes) {
+    return lanes == 0 || lanes == -1 || (lanes == 64 && (M::WAVE || M::QUAD)) || (lanes == I2C_LANES_QUAD && M::QUAD);
   }
+  // requests that leave the family open: a sweep the named kernels do not have runs what the model runs by default
+  static bool family_open(const Request r) { return r == REQ_DEFAULT || r == REQ_WAVE || r == REQ_QUAD || r == REQ_QUAD_FORWARD; }
+  static bool by_default(const Request r) { return r == REQ_DEFAULT || r == REQ_QUAD_FORWARD; }  // (of the sweeps behind the forward one)
+
   // per-cell targets [T][NZ][B] and temperatures [T][B] are addressed through 32-bit byte offsets of one buffer window by the
   // group, wave and quad kernels: beyond 4 GiB the offset would wrap and read the wrong cell (round-3 advice)
   static int window_32bit_ok(const I2cProblem* p) {
@@ -913,204 +945,303 @@ template <class M, typename R, typename S = R> struct Impl {
     if (p->alpha_cell && (long)p->T * (long)p->B * (long)sizeof(R) >= (1L << 32)) return I2C_EINVAL;
     return I2C_OK;
   }
-  // THE place that decides which kernel family serves a sweep (i2c_kernel_family() reports it): I2C_FAMILY_* or an error code.
-  //   explicit request (group_lanes = G or -1) -> that family or I2C_ENOTSUP;
-  //   default: the lane kernels, except (a) models that only have group kernels, (b) the hybrid default of the d >= 7 lane
-  //   models: the FORWARD sweep runs on the group kernels while the batch leaves every group wave a SIMD of its own
-  //   (measured, planar quadrotor d = 8 at B = 4096: forward 0.51 -> 0.40 ms, while its chunked lane backward stays the
-  //   faster one; the buffers of the families are the same, so the backward schedules are unaffected).
+  // a per-cell block of `elems` elements of `size` bytes stays inside the 2 GiB the predicated stores park their masked-off lanes behind
+  static bool below_2gib(const long elems, const I2cProblem* p, const size_t size) { return elems * (long)p->B * (long)size < (1L << 31); }
+  static constexpr long E_SWEEPS = C::E_FWD > C::E_POST ? C::E_FWD : C::E_POST;                   // forward messages, posterior
+  static constexpr long E_CLOSED = C::E_POST > C::E_PROP ? C::E_POST : C::E_PROP;                 // posterior, propagation
+  static constexpr long E_COMPOSITE = M::NX + M::NX * M::NX + sym(M::NX);                         // a chunk's composite map
+  // what the group form does not cover: other inference rules (the state estimator's is the unit cubature rule whatever the graph
+  // infers with; closed-loop propagation under Linearize() IS that rule: i2c.py:109-115); cells beyond 2 GiB (GIO::st_if)
+  static int group_supported(const I2cProblem* p, const int sweep) {
+    if (sweep != I2C_SWEEP_FILTER && p->inference != I2C_INF_CUBATURE && !(p->inference == I2C_INF_LINEARIZE && sweep == I2C_SWEEP_PROPAGATE))
+      return I2C_ENOTSUP;
+    if (!below_2gib(E_SWEEPS > C::E_PROP ? E_SWEEPS : C::E_PROP, p, sizeof(R))) return I2C_EINVAL;
+    return window_32bit_ok(p);
+  }
   // what the wave form covers: the cubature rule with lam = 0 (every shipped config: unit weights, no weight on the centre;
   // the centring of the pairwise sums relies on 2 d wi = 1), windows below 2 GiB (WIO::st_if)
-  static int wave_supported(const I2cProblem* p, const C& c) {
+  static int wave_supported(const I2cProblem* p, const bool unit) {
     if (p->inference == I2C_INF_LINEARIZE) {  // Linearize(): fp64 storage; needs a terminal observation like the lane form
       if (MIXED) return I2C_ENOTSUP;
       if (M::NZT == 0) return I2C_EINVAL;
     } else if (p->inference != I2C_INF_CUBATURE) {
       return I2C_ENOTSUP;
     }  // (a terminal state prior -- covariance control -- is the backward sweep's end of the chain: w_end_of_chain, round 4)
-    if (!unit_rule(c)) return I2C_ENOTSUP;
-    constexpr long EMAX = C::E_FWD > C::E_POST ? C::E_FWD : C::E_POST;
-    if (EMAX * (long)p->B * (long)sizeof(S) >= (1L << 31)) return I2C_EINVAL;
+    if (!unit) return I2C_ENOTSUP;
+    if (!below_2gib(E_SWEEPS, p, sizeof(S))) return I2C_EINVAL;
     return window_32bit_ok(p);
   }
-  // what the quad form (forward sweep) covers: the cubature rule with lam = 0 (unit weights, no weight on the centre: the centring
-  // of the pairwise sums relies on 2 d wi = 1, and the d = 8 models evaluate no centre point at all) for every model; any
-  // CubatureQuadrature(alpha, beta, kappa) for the models with sigma-point observations and a spare pair row (quad_general_exists:
-  // pendulum, cartpole, double cartpole -- the GENERAL variant, round 5); windows below 2 GiB
-  static int quad_supported(const I2cProblem* p, const C& c) {
+  // what the quad form covers: the cubature rule with lam = 0 for every model (the d = 8 models evaluate no centre point at all); any
+  // CubatureQuadrature(alpha, beta, kappa) for the models with the GENERAL variant (quad_general_exists, round 5); windows below 2 GiB
+  static int quad_supported(const I2cProblem* p, const bool unit) {
     if (p->inference != I2C_INF_CUBATURE) return I2C_ENOTSUP;
-    // cubature weights with lam != 0 (round 5): the GENERAL variant, for the models that have it (quad_general_exists)
-    if (!quad_general_exists<M>() && !unit_rule(c)) return I2C_ENOTSUP;
-    if constexpr (QG<M>::WIDE) {
-      // the d = 16 form addresses trajectory-major buffers only: the posterior / prior in that layout (the engine's default for
-      // the wave-capable models) and forward messages that the wave backward sweep reads
-      if (p->post_layout != 1) return I2C_ENOTSUP;
-      if constexpr (!HAS_WAVE) return I2C_ENOTSUP;
-      // (what wave_supported checks beyond the rule -- the window sizes -- follows below; general weights are this family's alone)
-    }
-    constexpr long EMAX = C::E_FWD > C::E_POST ? C::E_FWD : C::E_POST;
-    if (EMAX * (long)p->B * (long)sizeof(S) >= (1L << 31)) return I2C_EINVAL;
+    if (!quad_general_exists<M>() && !unit) return I2C_ENOTSUP;
+    // the d = 16 form addresses trajectory-major buffers only: the posterior / prior in that layout (the engine's default for the
+    // wave-capable models) and forward messages that the wave backward sweep reads
+    if (WIDE && (p->post_layout != 1 || !HAS_WAVE)) return I2C_ENOTSUP;
+    if (!below_2gib(E_SWEEPS, p, sizeof(S))) return I2C_EINVAL;
     return window_32bit_ok(p);
   }
-  // d <= 8: is the quad walker the DEFAULT walk pass of this problem? (no request, the chunked schedule is the batch's default and
-  // long enough to chunk, the batch inside the model's measured window)
-  static bool quad_chunk_default(const I2cProblem* p) {
-    if constexpr (HAS_QUAD_BACKWARD && !QG<M>::WIDE && LANE)
-      return (p->group_lanes == 0 || p->group_lanes == I2C_LANES_QUAD) && p->backward_mode == I2C_BWD_AUTO && p->inference == I2C_INF_CUBATURE &&
-             p->B >= quad_chunk_walk_min_b<M>::value && p->B <= quad_chunk_walk_max_b<M>::value && schedule(p->B, p->T, I2C_BWD_AUTO) == I2C_BWD_CHUNKED;
-    return false;
+  // the compose / stitch passes in the quad form: what the forward form covers, and composites (arithmetic-typed rows, which
+  // quad_supported's storage-typed bound does not cover under fp32 storage) inside the 2 GiB window of a chunk
+  static bool quad_passes_supported(const I2cProblem* p, const bool unit) {
+    return QUAD8 && quad_supported(p, unit) == I2C_OK && below_2gib(E_COMPOSITE, p, sizeof(R));
   }
-  // the compose / stitch passes of the chunked sigma-point schedule: I2C_FAMILY_QUAD when the quad walker was asked for by name
-  // (group_lanes = 64 with "chunked": the whole schedule on matrix instructions) or, by default, inside the model's
-  // quad_chunk_passes_min_b .. _max_b; I2C_FAMILY_LANE otherwise (i2c_kernel_family(problem, I2C_SWEEP_CHUNK_PASSES) reports it)
-  static int chunk_passes_family(const I2cProblem* p, const C& c) {
-    if constexpr (HAS_QUAD_BACKWARD && !QG<M>::WIDE && LANE) {
-      // (the composites are addressed through 32-bit offsets of one window per chunk, masked lanes parked at 2 GiB: arithmetic-typed
-      //  rows, which quad_supported's storage-typed bound does not cover under fp32 storage)
-      constexpr long EC = M::NX + M::NX * M::NX + sym(M::NX);
-      if (p->inference == I2C_INF_CUBATURE && quad_supported(p, c) == I2C_OK && EC * (long)p->B * (long)sizeof(R) < (1L << 31)) {
-        if (p->group_lanes == 64 && p->backward_mode == I2C_BWD_CHUNKED) return I2C_FAMILY_QUAD;
-        static const int forced_max = [] {  // experiment knob (not part of the ABI): overrides the model's window
-          const char* e = getenv("I2C_QUAD_PASSES_MAX_B");
-          return e ? atoi(e) : -2;
-        }();
-        const int min_b = forced_max > -2 ? 1 : quad_chunk_passes_min_b<M>::value, max_b = forced_max > -2 ? forced_max : quad_chunk_passes_max_b<M>::value;
-        if ((p->group_lanes == 0 || p->group_lanes == I2C_LANES_QUAD) && p->B >= min_b && p->B <= max_b) return I2C_FAMILY_QUAD;
-      }
-    }
-    return I2C_FAMILY_LANE;
+  // experiment knobs (not part of the ABI), read once per process: a batch size that overrides the model's window of the quad compose +
+  // stitch passes / of the quad stitch pass alone; -2: not set
+  static int env_knob(const char* name) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : -2;
   }
-  // the STITCH pass alone in the quad form, beyond the window of the pair: the pass is a chain of NC dependent steps on B / 64 lane
-  // wavefronts whatever the batch -- 0.85 us per quad step against 1.6 - 2.5 us per lane step (experiment: I2C_QUAD_STITCH_MAX_B)
-  static bool quad_stitch_alone(const I2cProblem* p, const C& c) {
-    if constexpr (HAS_QUAD_BACKWARD && !QG<M>::WIDE && LANE) {
-      static const int forced_max = [] {
-        const char* e = getenv("I2C_QUAD_STITCH_MAX_B");
-        return e ? atoi(e) : -2;
-      }();
-      constexpr long EC = M::NX + M::NX * M::NX + sym(M::NX);
-      const int max_b = forced_max > -2 ? forced_max : quad_chunk_stitch_max_b<M>::value;
-      return p->inference == I2C_INF_CUBATURE && (p->group_lanes == 0 || p->group_lanes == I2C_LANES_QUAD) && p->B <= max_b && quad_supported(p, c) == I2C_OK &&
-             EC * (long)p->B * (long)sizeof(R) < (1L << 31);
-    }
-    return false;
+  static int quad_passes_max_b_knob() {
+    static const int v = env_knob("I2C_QUAD_PASSES_MAX_B");
+    return v;
   }
-  static constexpr bool HAS_QUAD_CKF = HAS_QUAD && !MIXED && quad_ckf_exists<M>();  // the filter step of the d = 16 form
-  static constexpr bool HAS_QUAD_PROP = HAS_QUAD && !MIXED && quad_propagate_exists<M>();  // the closed-loop propagation of the d = 16 form
-  static int family(const I2cProblem* p, const C& c, const int sweep) {
-    if constexpr (HAS_GRID) {  // the Gauss-Hermite rule on a wavefront per trajectory: on request only (group_lanes = 64)
-      if (p->group_lanes == 64 && p->inference == I2C_INF_GAUSS_HERMITE &&
-          (sweep == I2C_SWEEP_FORWARD || sweep == I2C_SWEEP_BACKWARD || sweep == I2C_SWEEP_PROPAGATE))
-        return I2C_FAMILY_GRID;
+  static int quad_stitch_max_b_knob() {
+    static const int v = env_knob("I2C_QUAD_STITCH_MAX_B");
+    return v;
+  }
+
+  // The batch rule of the lane kernels. Small batches: the sequential depth decides -> chunked. Large ones: HBM traffic decides ->
+  // fused (the chunked form moves compose + stitch + walk = 1.44x the walk's bytes, PMC: pendulum 381 against 264.5 B per cell, double
+  // cartpole 1 914 against 1 177). The crossover is PER MODEL (M::BWD_FUSED_MIN_B, i2c_models.hpp), re-derived in round 5 from time AND
+  // traffic at B = 8192 .. 32768, beyond the 256 MB Infinity Cache (profiles/r5_backward_crossover.txt): pendulum 8192: chunked 0.111 /
+  // fused 0.175 ms, 16384: 0.237 / 0.193 (cartpole 0.72 / 0.99, 1.38 / 1.01; planar quadrotor 0.21 / 0.27, 0.38 / 0.30); double
+  // cartpole 16384: 1.67 / 1.86, 24576: 3.44 / 2.20. Models that only have group kernels run the fused walk.
+  static int lane_schedule(const int B, const int T, const int requested) {
+    // wave kernels: the fused walk, or on request the two-pass schedule (scan + one wave per (t, b) cell). Measured on MI355X
+    // (12-state quadrotor, T = 50): the two-pass form is SLOWER at every batch -- B = 256: 0.179 against 0.162 ms, B = 1024:
+    // 0.347 against 0.184 ms -- because with T times as many waves in flight the sweep is bound by the vector-memory
+    // pipeline: a wave's load touches one 8-byte element in each of 64 different [B]-contiguous rows (64 cache lines per
+    // instruction), which a lone wave per SIMD hides behind its dependent arithmetic and 50 waves per SIMD do not.
+    if (M::WAVE && M::GROUP_ONLY) return requested == I2C_BWD_TWO_PASS ? I2C_BWD_TWO_PASS : I2C_BWD_FUSED;
+    if (M::GROUP_ONLY) return I2C_BWD_FUSED;
+    int mode = requested;
+    if (mode == I2C_BWD_AUTO) mode = B < bwd_fused_min_b<M>::value ? I2C_BWD_CHUNKED : I2C_BWD_FUSED;
+    if (mode == I2C_BWD_CHUNKED && T < 8) mode = I2C_BWD_TWO_PASS;  // too short to chunk
+    return mode;
+  }
+  // d <= 8: is the quad walker the DEFAULT walk pass of this problem? (no backward request, the chunked schedule is the batch's default
+  // and long enough to chunk, the batch inside the model's measured window)
+  static bool quad_walker_default(const I2cProblem* p, const Request req) {
+    return QUAD8 && by_default(req) && p->backward_mode == I2C_BWD_AUTO && p->inference == I2C_INF_CUBATURE &&
+           p->B >= quad_chunk_walk_min_b<M>::value && p->B <= quad_chunk_walk_max_b<M>::value &&
+           lane_schedule(p->B, p->T, I2C_BWD_AUTO) == I2C_BWD_CHUNKED;
+  }
+
+  // The tail of every sweep's list: the one-lane kernels, or the group kernels -- asked for, the only ones the model has, or (forward
+  // sweep, nothing asked for) the hybrid default of the d >= 7 lane models while the batch leaves every group wave a SIMD of its own
+  // (measured, planar quadrotor d = 8 at B = 4096: forward 0.51 -> 0.40 ms, while its chunked lane backward stays the faster one; the
+  // buffers of the families are the same, so the backward schedules are unaffected).
+  static int lane_or_group(const I2cProblem* p, const Request req, const int sweep) {
+    if (req == REQ_NOT_OURS || (req == REQ_ONE_LANE && !LANE)) return I2C_ENOTSUP;
+    if constexpr (MIXED) {  // fp64 arithmetic on fp32-stored messages: the cubature EM path
+      const bool em = sweep == I2C_SWEEP_FORWARD || sweep == I2C_SWEEP_BACKWARD;
+      return (LANE && em && p->inference == I2C_INF_CUBATURE) ? I2C_FAMILY_LANE : I2C_ENOTSUP;
     }
-    if constexpr (HAS_QUAD_PROP) {  // the closed-loop propagation of a matrix-instruction graph: the quad form where it applies
-      // (unit cubature rule -- a Linearize() graph propagates with it, i2c.py:109-115 --, trajectory-major posterior)
-      if (sweep == I2C_SWEEP_PROPAGATE && (p->group_lanes == 0 || p->group_lanes == 64 || p->group_lanes == I2C_LANES_QUAD) &&
-          (p->inference == I2C_INF_CUBATURE || p->inference == I2C_INF_LINEARIZE) && p->post_layout == 1 &&
-          (unit_rule(c.rule_xu) || quad_general_exists<M>()) && window_32bit_ok(p) == I2C_OK) {
-        // (the posterior / propagation cells are addressed through 32-bit offsets of one window per cell, masked stores parked at
-        //  2 GiB like the other quad forms: beyond it the offsets would wrap silently -- refused here, as group_supported does)
-        constexpr long EP = C::E_POST > C::E_PROP ? C::E_POST : C::E_PROP;
-        if (EP * (long)p->B * (long)sizeof(R) >= (1L << 31)) return I2C_EINVAL;
-        return I2C_FAMILY_QUAD;
-      }
-    }
-    if constexpr (HAS_QUAD_CKF) {  // the state estimator of a matrix-instruction graph (default, 64 or I2C_LANES_QUAD): the quad filter step
-      if (sweep == I2C_SWEEP_FILTER && (p->group_lanes == 0 || p->group_lanes == 64 || p->group_lanes == I2C_LANES_QUAD)) return I2C_FAMILY_QUAD;
-    }
-    if constexpr (HAS_QUAD) {  // forward sweep: on request, or the model's default inside its batch window
-      bool asked = p->group_lanes == I2C_LANES_QUAD || (p->group_lanes == 64 && !M::WAVE);
-      bool sweep_ok = sweep == I2C_SWEEP_FORWARD;
-      int min_b = M::QUAD_FORWARD_MIN_B, max_b = M::QUAD_FORWARD_MAX_B;
-      if (sweep == I2C_SWEEP_BACKWARD && HAS_QUAD_BACKWARD) {
-        if constexpr (QG<M>::WIDE) {
-          // (the backward sweep of the d = 16 form: the fused walk, with the forward sweep -- an explicit two-pass request keeps the wave form)
-          sweep_ok = p->backward_mode != I2C_BWD_TWO_PASS;
-          min_b = M::QUAD_BACKWARD_MIN_B > M::QUAD_FORWARD_MIN_B ? M::QUAD_BACKWARD_MIN_B : M::QUAD_FORWARD_MIN_B;
-        } else {
-          // d <= 8 (round 6), two forms of backward_quad8_body. (i) The fused walk of four trajectories per wavefront, ONE pass over the
-          // forward messages: on request (group_lanes = 64 with the schedule left open or "fused"), or inside quad_backward_min_b .. _max_b
-          // (no in-tree model has one). (ii) The WALKER of the chunked schedule (compose / stitch / reduce stay lane kernels): on
-          // request (group_lanes = 64 with "chunked"), or the default inside the model's quad_chunk_walk_min_b .. _max_b where the chunked
-          // schedule is the batch's default (quad_chunk_default). An explicit "two_pass" is the lane kernels'.
-          // I2C_LANES_QUAD asks for the quad FORWARD sweep only: its backward sweep resolves as the default does (below).
-          asked = p->group_lanes == 64;
-          sweep_ok = asked ? p->backward_mode != I2C_BWD_TWO_PASS : p->backward_mode == I2C_BWD_AUTO;
-          min_b = quad_backward_min_b<M>::value, max_b = quad_backward_max_b<M>::value;
-          if (!asked && quad_chunk_default(p)) min_b = quad_chunk_walk_min_b<M>::value, max_b = quad_chunk_walk_max_b<M>::value;
-        }
-      }
-      // (d = 16 with general cubature weights: the wave kernels only have the unit rule -- the quad kernels at every batch size)
-      const bool general_wide = QG<M>::WIDE && quad_general_exists<M>() && !unit_rule(c);
-      if (sweep_ok && (asked || (p->group_lanes == 0 && ((p->B >= min_b && p->B <= max_b) || general_wide)))) {
-        const int rc = quad_supported(p, c);
-        if (rc == I2C_OK) return I2C_FAMILY_QUAD;
-        if (asked) return rc;
-      }
-    }
-    if (p->group_lanes == I2C_LANES_QUAD) {  // the other sweeps of an explicit quad request: the model's default family
-      I2cProblem q = *p;
-      q.group_lanes = 0;
-      return family(&q, c, sweep);
-    }
-    if constexpr (HAS_WAVE) {  // forward and backward sweeps: on request (group_lanes = 64) or as the model's default
-      if ((sweep == I2C_SWEEP_FORWARD || sweep == I2C_SWEEP_BACKWARD) &&
-          (p->group_lanes == 64 || p->group_lanes == 0)) {
-        const int rc = wave_supported(p, c);
-        if (rc == I2C_OK) return I2C_FAMILY_WAVE;
-        if (p->group_lanes == 64 || MIXED) return rc;
-      }
-    }
-    if constexpr (MIXED) {  // fp64 arithmetic on fp32-stored messages: the cubature EM path (one-lane, quad and wave kernels)
-      if (p->inference != I2C_INF_CUBATURE || use_group(p) != 0) return I2C_ENOTSUP;
-      if (sweep != I2C_SWEEP_FORWARD && sweep != I2C_SWEEP_BACKWARD) return I2C_ENOTSUP;
-      return LANE ? I2C_FAMILY_LANE : I2C_ENOTSUP;
-    }
-    int grp = use_group(p);
-    if (grp < 0) return grp;
+    bool group = req == REQ_GROUP || (family_open(req) && !LANE);
     if constexpr (HAS_GROUP && M::GROUP_FORWARD_AUTO) {
-      if (sweep == I2C_SWEEP_FORWARD && grp == 0 && p->group_lanes == 0 && (long)p->B * G <= I2C_GROUP_FORWARD_MAX_LANES &&
-          group_supported(p, c, sweep) == I2C_OK)
-        grp = 1;
+      if (!group && sweep == I2C_SWEEP_FORWARD && req == REQ_DEFAULT && (long)p->B * G <= I2C_GROUP_FORWARD_MAX_LANES &&
+          group_supported(p, sweep) == I2C_OK)
+        group = true;
     }
-    if (grp) {
+    if (group) {
       if constexpr (HAS_GROUP) {
-        const int rc = group_supported(p, c, sweep);
+        const int rc = group_supported(p, sweep);
         return rc != I2C_OK ? rc : I2C_FAMILY_GROUP;
       }
       return I2C_ENOTSUP;
     }
-    return LANE ? I2C_FAMILY_LANE : I2C_ENOTSUP;
+    return I2C_FAMILY_LANE;
   }
-  // The state estimator's rule is fixed, whatever the graph infers with: CubatureQuadrature(1, 0, 0) (mpc.py:121-123)
-  static I2cProblem filter_problem(const I2cProblem* p) {
+  // ... before it, for the forward and backward sweeps: the wave kernels, asked for or the model's default wherever they apply
+  static int wave_lane_or_group(const I2cProblem* p, const Request req, const bool unit, const int sweep) {
+    if constexpr (HAS_WAVE) {
+      if (family_open(req)) {
+        const int rc = wave_supported(p, unit);
+        if (rc == I2C_OK) return I2C_FAMILY_WAVE;
+        if (req == REQ_WAVE || MIXED) return rc;
+      }
+    }
+    return lane_or_group(p, req, sweep);
+  }
+  // The quad forward sweep: asked for, or the model's default inside its batch window -- and for d = 16 with general cubature weights
+  // at every batch size, since the wave kernels only have the unit rule. Asked for, its refusal is the answer.
+  static int forward_family(const I2cProblem* p, const Request req, const bool unit) {
+    if (req == REQ_GRID) return I2C_FAMILY_GRID;
+    if constexpr (HAS_QUAD) {
+      const bool asked = req == REQ_QUAD || req == REQ_QUAD_FORWARD;
+      const bool general_wide = WIDE && quad_general_exists<M>() && !unit;
+      if (asked || (req == REQ_DEFAULT && ((p->B >= M::QUAD_FORWARD_MIN_B && p->B <= M::QUAD_FORWARD_MAX_B) || general_wide))) {
+        const int rc = quad_supported(p, unit);
+        if (rc == I2C_OK) return I2C_FAMILY_QUAD;
+        if (asked) return rc;
+      }
+    }
+    return wave_lane_or_group(p, req, unit, I2C_SWEEP_FORWARD);
+  }
+  // The quad backward sweep. d = 16: the fused walk, with the forward sweep (from the larger of the two MIN_B on) -- an explicit two-pass
+  // request keeps the wave form. d <= 8 (round 6), two forms of backward_quad8_body: (i) the fused walk of four trajectories per
+  // wavefront, ONE pass over the forward messages: asked for (with the schedule left open or "fused"), or inside quad_backward_min_b ..
+  // _max_b (no in-tree model has one); (ii) the WALKER of the chunked schedule: asked for (with "chunked"), or the default inside the
+  // model's quad_chunk_walk_min_b .. _max_b where the chunked schedule is the batch's default (quad_walker_default). An explicit
+  // "two_pass" is the lane kernels'.
+  static int backward_family(const I2cProblem* p, const Request req, const bool unit) {
+    if (req == REQ_GRID) return I2C_FAMILY_GRID;
+    if constexpr (HAS_QUAD_BACKWARD) {
+      const bool asked = req == REQ_QUAD;
+      const bool general_wide = WIDE && quad_general_exists<M>() && !unit;
+      bool mode_ok, in_window;
+      if constexpr (WIDE) {
+        mode_ok = p->backward_mode != I2C_BWD_TWO_PASS;
+        in_window = p->B >= (M::QUAD_BACKWARD_MIN_B > M::QUAD_FORWARD_MIN_B ? M::QUAD_BACKWARD_MIN_B : M::QUAD_FORWARD_MIN_B) && p->B <= M::QUAD_FORWARD_MAX_B;
+      } else {
+        mode_ok = asked ? p->backward_mode != I2C_BWD_TWO_PASS : p->backward_mode == I2C_BWD_AUTO;
+        in_window = (p->B >= quad_backward_min_b<M>::value && p->B <= quad_backward_max_b<M>::value) || quad_walker_default(p, req);
+      }
+      if (mode_ok && (asked || (by_default(req) && (in_window || general_wide)))) {
+        const int rc = quad_supported(p, unit);
+        if (rc == I2C_OK) return I2C_FAMILY_QUAD;
+        if (asked) return rc;
+      }
+    }
+    return wave_lane_or_group(p, req, unit, I2C_SWEEP_BACKWARD);
+  }
+  // The closed-loop propagation of a matrix-instruction graph: the quad form where it applies (unit cubature rule -- `unit_xu`: a
+  // Linearize() graph propagates with it whatever the quad fields say --, trajectory-major posterior). The posterior / propagation
+  // cells are addressed through 32-bit offsets of one window per cell, masked stores parked at 2 GiB: beyond it, refused.
+  static int propagate_family(const I2cProblem* p, const Request req, const bool unit_xu) {
+    if (req == REQ_GRID) return I2C_FAMILY_GRID;
+    if constexpr (HAS_QUAD_PROP) {
+      if (family_open(req) && p->inference != I2C_INF_GAUSS_HERMITE && p->post_layout == 1 && (unit_xu || quad_general_exists<M>()) &&
+          window_32bit_ok(p) == I2C_OK)
+        return below_2gib(E_CLOSED, p, sizeof(R)) ? I2C_FAMILY_QUAD : I2C_EINVAL;
+    }
+    return lane_or_group(p, req, I2C_SWEEP_PROPAGATE);
+  }
+  // The state estimator: the quad filter step of a matrix-instruction graph. `req`: the request read under the estimator's own rule
+  static int filter_family(const I2cProblem* p, const Request req) {
+    if (HAS_QUAD_CKF && family_open(req)) return I2C_FAMILY_QUAD;
+    return lane_or_group(p, req, I2C_SWEEP_FILTER);
+  }
+  // The schedule of the backward sweep: the family that serves it, the inference rule, the storage type, then the batch rule of the
+  // lane kernels
+  static int backward_schedule(const I2cProblem* p, const Request req, const int fam) {
+    if (fam < 0) return fam;
+    const int lane_rule = lane_schedule(p->B, p->T, p->backward_mode);
+    if (fam == I2C_FAMILY_WAVE)  // the fused walk; the two-pass form on request (cubature rule)
+      return (lane_rule == I2C_BWD_TWO_PASS && p->inference == I2C_INF_CUBATURE) ? I2C_BWD_TWO_PASS : I2C_BWD_FUSED;
+    // d <= 8 quad: the chunked schedule with the quad walker when asked for by name, or as the model's default
+    if (QUAD8 && fam == I2C_FAMILY_QUAD && p->T >= 8 && (p->backward_mode == I2C_BWD_CHUNKED || quad_walker_default(p, req))) return I2C_BWD_CHUNKED;
+    if (fam != I2C_FAMILY_LANE) return I2C_BWD_FUSED;  // four trajectories / a group of lanes / a wavefront walk T-1..0
+    if (p->inference == I2C_INF_LINEARIZE && M::NZT == 0) return I2C_EINVAL;  // no terminal observation: the reference fails at i2c.py:500-501
+    if (p->inference != I2C_INF_CUBATURE) return (!MIXED && lane_rule == I2C_BWD_CHUNKED) ? I2C_BWD_CHUNKED : I2C_BWD_FUSED;  // no two-pass form
+    return lane_rule;
+  }
+  // The compose pass of the chunked sigma-point schedule in the quad form: with the quad walker asked for by name (group_lanes = 64 and
+  // "chunked": the whole schedule on matrix instructions) or, by default, inside the model's quad_chunk_passes_min_b .. _max_b
+  static bool quad_compose(const I2cProblem* p, const Request req, const bool unit) {
+    if (!quad_passes_supported(p, unit)) return false;
+    if (req == REQ_QUAD && p->backward_mode == I2C_BWD_CHUNKED) return true;
+    const int knob = quad_passes_max_b_knob();
+    const int min_b = knob > -2 ? 1 : quad_chunk_passes_min_b<M>::value, max_b = knob > -2 ? knob : quad_chunk_passes_max_b<M>::value;
+    return by_default(req) && p->B >= min_b && p->B <= max_b;
+  }
+  // ... and the STITCH pass alone, beyond that window: a chain of NC dependent steps on B / 64 lane wavefronts whatever the batch --
+  // 0.85 us per quad step against 1.6 - 2.5 us per lane step
+  static bool quad_stitch_alone(const I2cProblem* p, const Request req, const bool unit) {
+    const int knob = quad_stitch_max_b_knob();
+    return by_default(req) && p->B <= (knob > -2 ? knob : quad_chunk_stitch_max_b<M>::value) && quad_passes_supported(p, unit);
+  }
+
+  // THE place that decides which kernel family and which backward schedule serve a problem (i2c_kernel_family() and
+  // i2c_backward_schedule() report it; every entry point below dispatches from it)
+  static Plan resolve(const I2cProblem* p) {
+    const Rule<R> rule_xu = make_rule<R>(p, C::D), rule_x = make_rule<R>(p, C::NX);
+    const bool unit_xu = unit_rule(rule_xu), unit = unit_xu && unit_rule(rule_x);
+    const Request req = request(p->group_lanes, p->inference);
+    Plan pl;
+    pl.rule = p->inference;
+    pl.forward = forward_family(p, req, unit);
+    pl.backward = backward_family(p, req, unit);
+    pl.propagate = propagate_family(p, req, unit_xu || p->inference == I2C_INF_LINEARIZE);
+    // (the state estimator's rule is fixed, whatever the graph infers with -- CubatureQuadrature(1, 0, 0), mpc.py:121-123 --, so the
+    //  filter step is no grid sweep: under a grid request it sees what 64 names under the cubature rule)
+    pl.filter = filter_family(p, req == REQ_GRID ? request(p->group_lanes, I2C_INF_CUBATURE) : req);
+    pl.schedule = backward_schedule(p, req, pl.backward);
+    const bool chunked = pl.schedule == I2C_BWD_CHUNKED;
+    pl.walker = chunked ? pl.backward : I2C_ENOTSUP;
+    pl.compose = pl.stitch = pl.schedule < 0 ? pl.schedule : I2C_ENOTSUP;
+    if (chunked && p->inference == I2C_INF_CUBATURE) {
+      pl.compose = quad_compose(p, req, unit) ? I2C_FAMILY_QUAD : I2C_FAMILY_LANE;
+      pl.stitch = (pl.compose == I2C_FAMILY_QUAD || quad_stitch_alone(p, req, unit)) ? I2C_FAMILY_QUAD : I2C_FAMILY_LANE;
+    }
+    // (the fp32-storage path has never set the flag)
+    pl.fwd_tm = !MIXED && pl.forward == I2C_FAMILY_QUAD && ((M::WAVE && pl.backward == I2C_FAMILY_WAVE) || (HAS_QUAD_BACKWARD && pl.backward == I2C_FAMILY_QUAD));
+    pl.fusable = LANE && C::D <= 5 && p->inference == I2C_INF_CUBATURE && pl.forward == I2C_FAMILY_LANE && pl.propagate == I2C_FAMILY_LANE &&
+                 rule_xu.unit && rule_x.unit && !(p->z_per_cell && p->z) && !p->alpha_cell && p->t0 == 0;
+    return pl;
+  }
+  static int plan(const I2cProblem* p) { return resolve(p).schedule; }
+  static int family_of(const I2cProblem* p, const int sweep) {
+    const Plan pl = resolve(p);
+    const int of_sweep[] = {pl.forward, pl.backward, pl.propagate, pl.filter, pl.compose, pl.stitch};  // I2C_SWEEP_FORWARD .. _CHUNK_STITCH
+    return of_sweep[sweep];
+  }
+  // the schedule that runs: a chunked answer without its workspace (I2cProblem.work) falls back to the two-pass form, or -- the quad
+  // walker and the rules without a two-pass form -- to the fused walk
+  static int schedule_with(const Plan& pl, const bool workspace) {
+    if (pl.schedule != I2C_BWD_CHUNKED || workspace) return pl.schedule;
+    return (pl.rule == I2C_INF_CUBATURE && pl.walker != I2C_FAMILY_QUAD) ? I2C_BWD_TWO_PASS : I2C_BWD_FUSED;
+  }
+
+  // ---- the constants of a call ---------------------------------------------------------------------------------------------------
+  static I2cProblem with_unit_rule(const I2cProblem* p) {
     I2cProblem q = *p;
-    q.inference = I2C_INF_CUBATURE;
     q.quad_alpha = 1.0, q.quad_beta = 0.0, q.quad_kappa = 0.0;
     return q;
   }
-  static int family_of(const I2cProblem* p, int sweep) {
-    I2cProblem q = sweep == I2C_SWEEP_FILTER ? filter_problem(p) : *p;
-    if (sweep == I2C_SWEEP_PROPAGATE && p->inference == I2C_INF_LINEARIZE) q.quad_alpha = 1.0, q.quad_beta = 0.0, q.quad_kappa = 0.0;  // (as propagate())
-    const C c = make_consts<M, R>(&q, 0.0, 0);
-    if (sweep == I2C_SWEEP_CHUNK_PASSES) {  // the compose / stitch passes: of a problem whose backward sweep runs the chunked sigma-point schedule
-      const int mode = plan(&q);
-      if (mode < 0) return mode;
-      if (mode != I2C_BWD_CHUNKED || q.inference != I2C_INF_CUBATURE) return I2C_ENOTSUP;
-      return chunk_passes_family(&q, c);
-    }
-    if (sweep == I2C_SWEEP_CHUNK_STITCH) {  // the stitch pass of that schedule: with the compose pass, or alone inside its own window
-      const int mode = plan(&q);
-      if (mode < 0) return mode;
-      if (mode != I2C_BWD_CHUNKED || q.inference != I2C_INF_CUBATURE) return I2C_ENOTSUP;
-      return (chunk_passes_family(&q, c) == I2C_FAMILY_QUAD || quad_stitch_alone(&q, c)) ? I2C_FAMILY_QUAD : I2C_FAMILY_LANE;
-    }
-    return family(&q, c, sweep);
+  static C forward_consts(const I2cProblem* p) { return make_consts<M, R>(p, 0.0, p->inference == I2C_INF_LINEARIZE ? p->expert_controller : 0); }
+  // under Linearize() the closed-loop propagation IS CubatureQuadrature(1, 0, 0) whatever the caller left in the quad fields (i2c.py:109-115)
+  static C propagate_consts(const I2cProblem* p, const int use_expert) {
+    if (p->inference != I2C_INF_LINEARIZE) return make_consts<M, R>(p, 0.0, use_expert);
+    const I2cProblem q = with_unit_rule(p);
+    return make_consts<M, R>(&q, 0.0, use_expert);
+  }
+  // ... and so is the state estimator's rule, whatever the graph infers with
+  static C filter_consts(const I2cProblem* p) {
+    I2cProblem q = with_unit_rule(p);
+    q.inference = I2C_INF_CUBATURE;
+    return make_consts<M, R>(&q, 0.0, 0);
   }
 
-  // the sigma-point forward sweep of the one-lane kernels, for either storage type
-  static int forward_lane(const I2cProblem* p, const C& c, const FwdArgs<R, S>& a, void* stream) {
+  // ---- the sweeps: each written once for either storage type, dispatched from the plan --------------------------------------------
+  static int run_forward(const I2cProblem* p, const Plan& pl, const C& c, const void* prior, void* fwd, void* prior_out, int32_t* status,
+                         void* stream) {
+    if (pl.forward < 0) return pl.forward;
+    const FwdArgs<R, S> a{(const S*)prior, (S*)fwd, (S*)prior_out, (const R*)p->x0, (const R*)p->sig_x0,
+                          (const R*)p->z,  (const R*)p->alpha, (const R*)p->alpha_cell, p->feedforward, status, p->expert};
+    if (pl.forward == I2C_FAMILY_WAVE) {
+      if constexpr (HAS_WAVE) return launch_wave<WK_FORWARD, M, R, S>(c, a, stream);
+    }
+    if (pl.forward == I2C_FAMILY_QUAD) {
+      if constexpr (HAS_QUAD) {
+        C cq = c;
+        cq.fwd_tm = pl.fwd_tm;
+        return launch_quad_forward<M, R, S>(cq, a, stream);
+      }
+    }
+    if (pl.forward == I2C_FAMILY_GROUP) {
+      if constexpr (HAS_GROUP) return launch_group<GK_FORWARD, M, R, G>(c, nullptr, a, stream);
+    }
+    if (pl.forward == I2C_FAMILY_GRID) {
+      if constexpr (HAS_GRID) return launch_grid<GRK_FORWARD, M, R>(c, a, stream);
+    }
     if constexpr (LANE) {
+      if constexpr (!MIXED) {  // (these two rules: fp64 storage)
+        if (pl.rule == I2C_INF_LINEARIZE) return launch(k_forward_lin<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
+        if (pl.rule == I2C_INF_GAUSS_HERMITE) return launch(k_forward<M, R, false, true>, p->B, 1, LANE_BLOCK, stream, c, a, LANE_BLOCK);
+      }
 #ifdef I2C_HOST_SIM
       const int lanes = LANE_BLOCK;
 #else
@@ -1122,112 +1253,8 @@ template <class M, typename R, typename S = R> struct Impl {
     }
     return I2C_ENOTSUP;
   }
-
-  static int forward(const I2cProblem* p, const void* prior, void* fwd, void* prior_out, int32_t* status,
-                     void* stream) {
-    const C c = make_consts<M, R>(p, 0.0, p->inference == I2C_INF_LINEARIZE ? p->expert_controller : 0);
-    if constexpr (MIXED) {  // fp64 arithmetic on fp32-stored messages: the cubature path (one-lane, quad and wave kernels)
-      const int fam = family(p, c, I2C_SWEEP_FORWARD);
-      if (fam < 0) return fam;
-      FwdArgs<R, S> am{(const S*)prior, (S*)fwd, (S*)prior_out, (const R*)p->x0, (const R*)p->sig_x0,
-                       (const R*)p->z,  (const R*)p->alpha, (const R*)p->alpha_cell, p->feedforward, status, p->expert};
-      if (fam == I2C_FAMILY_WAVE) {
-        if constexpr (HAS_WAVE) return launch_wave<WK_FORWARD, M, R, S>(c, am, stream);
-      }
-      if (fam == I2C_FAMILY_QUAD) {
-        if constexpr (HAS_QUAD) return launch_quad_forward<M, R, S>(c, am, stream);
-      }
-      return forward_lane(p, c, am, stream);
-    } else {
-      return forward_any(p, c, prior, fwd, prior_out, status, stream);
-    }
-  }
-  static int forward_any(const I2cProblem* p, const C& c, const void* prior, void* fwd, void* prior_out, int32_t* status,
-                         void* stream) {
-    FwdArgs<R> a{(const R*)prior, (R*)fwd, (R*)prior_out, (const R*)p->x0, (const R*)p->sig_x0,
-                 (const R*)p->z,  (const R*)p->alpha, (const R*)p->alpha_cell, p->feedforward, status, p->expert};
-    const int fam = family(p, c, I2C_SWEEP_FORWARD);
-    if (fam < 0) return fam;
-    if (fam == I2C_FAMILY_WAVE) {
-      if constexpr (HAS_WAVE && !MIXED) return launch_wave<WK_FORWARD, M, R, R>(c, a, stream);
-    }
-    if (fam == I2C_FAMILY_QUAD) {
-      if constexpr (HAS_QUAD) {  // the forward messages go where the backward family of this problem reads them
-        C cq = c;
-        const int fb = family(p, c, I2C_SWEEP_BACKWARD);
-        cq.fwd_tm = ((M::WAVE && fb == I2C_FAMILY_WAVE) || (HAS_QUAD_BACKWARD && fb == I2C_FAMILY_QUAD)) ? 1 : 0;
-        return launch_quad_forward<M, R, R>(cq, a, stream);
-      }
-    }
-    if (fam == I2C_FAMILY_GROUP) {
-      if constexpr (HAS_GROUP) return launch_group<GK_FORWARD, M, R, G>(c, nullptr, a, stream);
-    }
-    if (fam == I2C_FAMILY_GRID) {
-      if constexpr (HAS_GRID) return launch_grid<GRK_FORWARD, M, R>(c, a, stream);
-    }
-    if constexpr (LANE) {
-      if (p->inference == I2C_INF_LINEARIZE) return launch(k_forward_lin<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
-      if (p->inference == I2C_INF_GAUSS_HERMITE)
-        return launch(k_forward<M, R, false, true>, p->B, 1, LANE_BLOCK, stream, c, a, LANE_BLOCK);
-      if constexpr (!MIXED) return forward_lane(p, c, a, stream);
-    }
-    return I2C_ENOTSUP;
-  }
-
-  // Small batches: the sequential depth decides -> chunked. Large ones: HBM traffic decides -> fused (the chunked form moves
-  // compose + stitch + walk = 1.44x the walk's bytes, PMC: pendulum 381 against 264.5 B per cell, double cartpole 1 914 against
-  // 1 177). The crossover is PER MODEL (M::BWD_FUSED_MIN_B, i2c_models.hpp), re-derived in round 5 from time AND traffic at
-  // B = 8192 .. 32768, beyond the 256 MB Infinity Cache (profiles/r5_backward_crossover.txt): pendulum 8192: chunked 0.111 /
-  // fused 0.175 ms, 16384: 0.237 / 0.193 (cartpole 0.72 / 0.99, 1.38 / 1.01; planar quadrotor 0.21 / 0.27, 0.38 / 0.30); double
-  // cartpole 16384: 1.67 / 1.86, 24576: 3.44 / 2.20. Models that only have group
-  // kernels run the fused walk.
-  static int schedule(int B, int T, int requested) {
-    if (M::WAVE && M::GROUP_ONLY) {
-      // wave kernels: the fused walk, or on request the two-pass schedule (scan + one wave per (t, b) cell). Measured on MI355X
-      // (12-state quadrotor, T = 50): the two-pass form is SLOWER at every batch -- B = 256: 0.179 against 0.162 ms, B = 1024:
-      // 0.347 against 0.184 ms -- because with T times as many waves in flight the sweep is bound by the vector-memory
-      // pipeline: a wave's load touches one 8-byte element in each of 64 different [B]-contiguous rows (64 cache lines per
-      // instruction), which a lone wave per SIMD hides behind its dependent arithmetic and 50 waves per SIMD do not.
-      return requested == I2C_BWD_TWO_PASS ? I2C_BWD_TWO_PASS : I2C_BWD_FUSED;
-    }
-    if (M::GROUP_ONLY) return I2C_BWD_FUSED;
-    int mode = requested;
-    if (mode == I2C_BWD_AUTO)
-      mode = B < bwd_fused_min_b<M>::value ? I2C_BWD_CHUNKED : I2C_BWD_FUSED;
-    if (mode == I2C_BWD_CHUNKED && T < 8) mode = I2C_BWD_TWO_PASS;  // too short to chunk
-    return mode;
-  }
-  // THE place that decides which backward schedule runs for a problem (i2c_backward_schedule() reports it): the family that
-  // serves the sweep, the inference rule, the storage type, then the batch-size rule of the lane kernels. An error code when
-  // the sweep would refuse the problem. (What it assumes: the workspaces of its answer are supplied -- pick_mode.)
-  static int plan(const I2cProblem* p) {
-    const C c = make_consts<M, R>(p, 0.0, 0);
-    const int fam = family(p, c, I2C_SWEEP_BACKWARD);
-    if (fam < 0) return fam;
-    const int lane_rule = schedule(p->B, p->T, p->backward_mode);
-    if (fam == I2C_FAMILY_WAVE)  // the fused walk; the two-pass form on request (cubature rule)
-      return (lane_rule == I2C_BWD_TWO_PASS && p->inference == I2C_INF_CUBATURE) ? I2C_BWD_TWO_PASS : I2C_BWD_FUSED;
-    if constexpr (HAS_QUAD_BACKWARD && !QG<M>::WIDE && LANE) {
-      // d <= 8 quad: the fused walk, or the chunked schedule with the quad walker (compose / stitch / reduce are the lane kernels) --
-      // when asked for by name, or as the model's default inside its quad_chunk_walk_min_b .. _max_b
-      if (fam == I2C_FAMILY_QUAD && p->T >= 8 && (p->backward_mode == I2C_BWD_CHUNKED || quad_chunk_default(p))) return I2C_BWD_CHUNKED;
-    }
-    if (fam == I2C_FAMILY_QUAD || fam == I2C_FAMILY_GROUP || fam == I2C_FAMILY_GRID) return I2C_BWD_FUSED;  // four trajectories / a group of lanes / a wavefront walk T-1..0
-    if (!LANE) return I2C_ENOTSUP;
-    if (p->inference == I2C_INF_LINEARIZE) {
-      if (M::NZT == 0) return I2C_EINVAL;  // no terminal observation: the reference fails at i2c.py:500-501
-      return (!MIXED && lane_rule == I2C_BWD_CHUNKED) ? I2C_BWD_CHUNKED : I2C_BWD_FUSED;
-    }
-    if (p->inference == I2C_INF_GAUSS_HERMITE) return (!MIXED && lane_rule == I2C_BWD_CHUNKED) ? I2C_BWD_CHUNKED : I2C_BWD_FUSED;
-    return lane_rule;
-  }
-  static int pick_mode(const I2cProblem* p) {
-    int mode = plan(p);
-    if (mode == I2C_BWD_CHUNKED && !p->work) {  // no workspace
-      const C c = make_consts<M, R>(p, 0.0, 0);
-      mode = (p->inference == I2C_INF_CUBATURE && family(p, c, I2C_SWEEP_BACKWARD) != I2C_FAMILY_QUAD) ? I2C_BWD_TWO_PASS : I2C_BWD_FUSED;
-    }
-    return mode;
+  static int forward(const I2cProblem* p, const void* prior, void* fwd, void* prior_out, int32_t* status, void* stream) {
+    return run_forward(p, resolve(p), forward_consts(p), prior, fwd, prior_out, status, stream);
   }
 
   // `fuse` (i2c_learn only): run the M-step inside the reduction kernel of the two-pass / chunked schedules.
@@ -1243,183 +1270,128 @@ template <class M, typename R, typename S = R> struct Impl {
   static const R* terminal_alpha(const I2cProblem* p, const C& c) {
     return p->alpha_cell ? (const R*)p->alpha_cell + (long)c.row(p->T - 1) * (long)p->B : (const R*)p->alpha;
   }
-  static int backward(const I2cProblem* p, const void* fwd, void* xm, void* post, void* zpost, void* cell_stats,
-                      void* term_stats, int32_t* status, void* stream) {
-    return backward_impl(p, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, nullptr);
-  }
-  static int backward_impl(const I2cProblem* p, const void* fwd, void* xm, void* post, void* zpost, void* cell_stats,
-                           void* term_stats, int32_t* status, void* stream, MstepFuse* fuse) {
-    const C c = make_consts<M, R>(p, fuse ? fuse->tol : 0.0, 0);
-    MstepArgs<R> ms{(const R*)term_stats, fuse ? (R*)p->alpha : nullptr, fuse ? (R*)fuse->stats_out : nullptr,
-                    fuse ? fuse->update : 0};
-    if constexpr (MIXED) {
-      const int fam = family(p, c, I2C_SWEEP_BACKWARD);
-      if (fam < 0) return fam;
-      CellArgs<R, S> am{(const S*)fwd, (const S*)xm,   (const R*)p->z, (S*)post,  (S*)zpost,
-                        (R*)cell_stats, (R*)term_stats, (R*)p->temp,    status,   terminal_alpha(p, c)};
-      if (fam == I2C_FAMILY_WAVE) return backward_wave(p, c, am, ms, fuse, stream);
-      if (fam == I2C_FAMILY_QUAD) {
-        if constexpr (HAS_QUAD_BACKWARD) {
-          if constexpr (!QG<M>::WIDE && LANE) {
-            if (pick_mode(p) == I2C_BWD_CHUNKED) return backward_chunked(p, c, am, ms, fuse, stream, true);
-          }
-          return launch_quad_backward<M, R, S>(c, am, stream);
-        }
+  // `c`: the constants of the call with the M-step's tolerance where `fuse` is set
+  static int run_backward(const I2cProblem* p, const Plan& pl, const C& c, const void* fwd, void* xm, void* post, void* zpost, void* cell_stats,
+                          void* term_stats, int32_t* status, void* stream, MstepFuse* fuse) {
+    if (pl.backward < 0) return pl.backward;
+    if (pl.schedule < 0) return pl.schedule;
+    const MstepArgs<R> ms{(const R*)term_stats, fuse ? (R*)p->alpha : nullptr, fuse ? (R*)fuse->stats_out : nullptr, fuse ? fuse->update : 0};
+    const CellArgs<R, S> a{(const S*)fwd,  (const S*)xm,   (const R*)p->z, (S*)post, (S*)zpost,
+                           (R*)cell_stats, (R*)term_stats, (R*)p->temp,    status,   terminal_alpha(p, c)};
+    const int mode = schedule_with(pl, p->work != nullptr);
+    int rc = I2C_ENOTSUP;
+    if (pl.backward == I2C_FAMILY_WAVE) {
+      // the fused walk; two-pass (scan, one wave per cell, reduction -- with the M-step riding on it in i2c_learn) when that schedule
+      // is asked for and its workspaces exist
+      if constexpr (HAS_WAVE) {
+        if (mode != I2C_BWD_TWO_PASS || !a.xm || !a.cell_stats) return launch_wave<WK_BACKWARD, M, R, S>(c, a, stream);
+        rc = launch_wave<WK_SCAN, M, R, S>(c, a, stream);
+        if (rc == I2C_OK) rc = launch_wave<WK_CELL, M, R, S>(c, a, stream);
+        if (rc == I2C_OK) rc = launch_reduce<M, R>(c, a, ms, p->T, stream);
+        if (fuse) fuse->done = true;
       }
-      return backward_lane(p, c, am, ms, fuse, stream);
-    } else {
-      return backward_any(p, c, ms, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, fuse);
-    }
-  }
-  // the wave family's backward sweep: two-pass (scan, one wave per cell, reduction -- with the M-step riding on it in
-  // i2c_learn) when that schedule is asked for / the default and its workspaces exist; the fused walk otherwise
-  template <class CA>
-  static int backward_wave(const I2cProblem* p, const C& c, const CA& a, const MstepArgs<R>& ms, MstepFuse* fuse, void* stream) {
-    if constexpr (HAS_WAVE) {
-      const bool two_pass = plan(p) == I2C_BWD_TWO_PASS && a.xm && a.cell_stats;
-      if (!two_pass) return launch_wave<WK_BACKWARD, M, R, S>(c, a, stream);
-      int rc = launch_wave<WK_SCAN, M, R, S>(c, a, stream);
-      if (rc == I2C_OK) rc = launch_wave<WK_CELL, M, R, S>(c, a, stream);
-      if (rc == I2C_OK) rc = launch_reduce<M, R>(c, a, ms, p->T, stream);
-      if (fuse) fuse->done = true;
       return rc;
     }
-    return I2C_ENOTSUP;
-  }
-  static int backward_any(const I2cProblem* p, const C& c, const MstepArgs<R>& ms, const void* fwd, void* xm, void* post,
-                          void* zpost, void* cell_stats, void* term_stats, int32_t* status, void* stream, MstepFuse* fuse) {
-    CellArgs<R> a{(const R*)fwd, (const R*)xm,   (const R*)p->z, (R*)post,  (R*)zpost,
-                  (R*)cell_stats, (R*)term_stats, (R*)p->temp,    status,   terminal_alpha(p, c)};
-    const int fam = family(p, c, I2C_SWEEP_BACKWARD);
-    if (fam < 0) return fam;
-    if (fam == I2C_FAMILY_WAVE) {
-      if constexpr (!MIXED) return backward_wave(p, c, a, ms, fuse, stream);
-    }
-    if (fam == I2C_FAMILY_QUAD) {
+    if (pl.backward == I2C_FAMILY_QUAD) {
       if constexpr (HAS_QUAD_BACKWARD) {
-        if constexpr (!QG<M>::WIDE && LANE && !MIXED) {
-          if (pick_mode(p) == I2C_BWD_CHUNKED) return backward_chunked(p, c, a, ms, fuse, stream, true);
+        if constexpr (QUAD8) {
+          if (mode == I2C_BWD_CHUNKED) return backward_chunked(p, pl, c, a, ms, fuse, stream);
         }
-        return launch_quad_backward<M, R, R>(c, a, stream);
+        return launch_quad_backward<M, R, S>(c, a, stream);
       }
     }
-    if (fam == I2C_FAMILY_GROUP) {  // one schedule: the group walks T-1..0 (the fused form); backward_mode is ignored
+    if (pl.backward == I2C_FAMILY_GROUP) {  // one schedule: the group walks T-1..0 (the fused form)
       if constexpr (HAS_GROUP) return launch_group<GK_BACKWARD, M, R, G>(c, nullptr, a, stream);
     }
-    if (fam == I2C_FAMILY_GRID) {  // one schedule as well: the fused walk, no workspace
+    if (pl.backward == I2C_FAMILY_GRID) {  // one schedule as well: the fused walk, no workspace
       if constexpr (HAS_GRID) return launch_grid<GRK_BACKWARD, M, R>(c, a, stream);
     }
     if constexpr (LANE) {
-      if (p->inference == I2C_INF_LINEARIZE) {  // a lane per trajectory walks T-1..0, or (small batches) the chunked form
-        if (M::NZT == 0) return I2C_EINVAL;     // no terminal observation: the reference fails at i2c.py:500-501
+      if (mode == I2C_BWD_CHUNKED) return backward_chunked(p, pl, c, a, ms, fuse, stream);
+      if (mode == I2C_BWD_FUSED) {  // a lane per trajectory walks T-1..0
         if constexpr (!MIXED) {
-          if (pick_mode(p) == I2C_BWD_CHUNKED) {  // (pick_mode: asked for or the default below I2C_BWD_FUSED_MIN_B, with a workspace)
-            const ChunkArgs<R, R> ch = chunk_args<M>(p, a);
-            int rc = launch(k_chunk_compose<M, R, R>, p->B, ch.n_chunks, LANE_BLOCK, stream, c, ch);
-            if (rc == I2C_OK) rc = launch(k_chunk_stitch_lin<M, R>, p->B, 1, LANE_BLOCK, stream, c, ch);
-            if (rc == I2C_OK) rc = launch(k_chunk_walk_lin<M, R>, p->B, ch.n_chunks, LANE_BLOCK, stream, c, ch);
-            if (rc == I2C_OK) rc = launch(k_chunk_reduce_lin<M, R>, p->B, 1, LANE_BLOCK, stream, c, ch, ms);
-            if (fuse) fuse->done = true;
-            return rc;
-          }
+          if (pl.rule == I2C_INF_LINEARIZE) return launch(k_bwd_lin<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
+          if (pl.rule == I2C_INF_GAUSS_HERMITE) return launch(k_bwd_fused<M, R, true>, p->B, 1, LANE_BLOCK, stream, c, a);
         }
-        return launch(k_bwd_lin<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
-      }
-      if (p->inference == I2C_INF_GAUSS_HERMITE) {  // the fused walk with the grid transform, or (small batches) the chunked form:
-        if constexpr (!MIXED) {                     // the composition of the x-marginal recursion has no transform in it
-          if (pick_mode(p) == I2C_BWD_CHUNKED) {
-            const ChunkArgs<R, R> ch = chunk_args<M>(p, a);
-            C cr = c;  // reduction over chunks instead of cells: same kernel, T := number of chunks
-            cr.T = ch.n_chunks;
-            CellArgs<R> ared = a;
-            ared.cell_stats = ch.part;
-            int rc = launch(k_chunk_compose<M, R, R>, p->B, ch.n_chunks, LANE_BLOCK, stream, c, ch);
-            if (rc == I2C_OK) rc = launch(k_chunk_stitch<M, R, R, true>, p->B, 1, LANE_BLOCK, stream, c, ch);
-            if (rc == I2C_OK) rc = launch(k_chunk_walk<M, R, R, false, true>, p->B, ch.n_chunks, LANE_BLOCK, stream, c, ch);
-            if (rc == I2C_OK) rc = launch_reduce<M, R>(cr, ared, ms, p->T, stream);
-            if (fuse) fuse->done = true;
-            return rc;
-          }
-        }
-        return launch(k_bwd_fused<M, R, true>, p->B, 1, LANE_BLOCK, stream, c, a);
-      }
-      if constexpr (!MIXED) return backward_lane(p, c, a, ms, fuse, stream);
-    }
-    return I2C_ENOTSUP;
-  }
-  // the chunked schedule of the sigma-point backward sweep: compose (one lane per trajectory and chunk) + stitch + walk + reduce; the
-  // walk pass on the lane walker, or -- quad_walk, d <= 8 -- on the quad walker (four trajectories per wavefront and chunk)
-  static int backward_chunked(const I2cProblem* p, const C& c, const CellArgs<R, S>& a, const MstepArgs<R>& ms, MstepFuse* fuse, void* stream,
-                              const bool quad_walk) {
-    if constexpr (LANE) {
-      const ChunkArgs<R, S> ch = chunk_args<M>(p, a);
-      C cr = c;  // reduction over chunks instead of cells: same kernel, T := number of chunks
-      cr.T = ch.n_chunks;
-      CellArgs<R, S> ared = a;
-      ared.cell_stats = ch.part;
-      int rc;
-      bool quad_compose = false, quad_stitch = false;
-      if constexpr (HAS_QUAD_BACKWARD && !QG<M>::WIDE) {
-        quad_compose = chunk_passes_family(p, c) == I2C_FAMILY_QUAD;  // compose + stitch, four trajectories per wavefront
-        quad_stitch = quad_compose || quad_stitch_alone(p, c);       // ... or the stitch pass alone (a chain of NC steps whatever the batch)
-      }
-      if (quad_compose) {
-        if constexpr (HAS_QUAD_BACKWARD && !QG<M>::WIDE) rc = launch_quad_chunk_compose<M, R, S>(c, ch, stream);
-        else rc = I2C_ENOTSUP;
-      } else {
-        rc = launch(k_chunk_compose<M, R, S>, p->B, ch.n_chunks, LANE_BLOCK, stream, c, ch);
-      }
-      if (rc == I2C_OK) {
-        if (quad_stitch) {
-          if constexpr (HAS_QUAD_BACKWARD && !QG<M>::WIDE) rc = launch_quad_chunk_stitch<M, R, S>(c, ch, stream);
-          else rc = I2C_ENOTSUP;
-        } else {
-          rc = launch(k_chunk_stitch<M, R, S>, p->B, 1, LANE_BLOCK, stream, c, ch);
-        }
-      }
-      if (rc == I2C_OK) {
-        if (quad_walk) {
-          if constexpr (HAS_QUAD_BACKWARD && !QG<M>::WIDE) rc = launch_quad_chunk_walk<M, R, S>(c, ch, stream);
-          else rc = I2C_ENOTSUP;
-        } else {
-          const bool lean = I2C_WALK_LEAN && !a.xm && !a.zpost && !a.cell_stats && !c.z_per_cell;  // see chunk_walk_body
-          rc = lean ? launch(k_chunk_walk<M, R, S, true>, p->B, ch.n_chunks, LANE_BLOCK, stream, c, ch)
-                    : launch(k_chunk_walk<M, R, S>, p->B, ch.n_chunks, LANE_BLOCK, stream, c, ch);
-        }
-      }
-      if (rc == I2C_OK) rc = launch_reduce<M, R>(cr, ared, ms, p->T, stream);
-      if (fuse) fuse->done = true;
-      return rc;
-    }
-    return I2C_ENOTSUP;
-  }
-  // the three schedules of the sigma-point backward sweep of the one-lane kernels, for either storage type
-  static int backward_lane(const I2cProblem* p, const C& c, const CellArgs<R, S>& a, const MstepArgs<R>& ms, MstepFuse* fuse,
-                           void* stream) {
-    if constexpr (LANE) {
-      const int mode = pick_mode(p);
-      if (mode == I2C_BWD_FUSED) {
         const bool lean = I2C_WALK_LEAN && !a.xm && !a.zpost && !a.cell_stats && !c.z_per_cell;  // see chunk_walk_body
         return lean ? launch(k_bwd_fused<M, R, false, S, true>, p->B, 1, LANE_BLOCK, stream, c, a)
                     : launch(k_bwd_fused<M, R, false, S>, p->B, 1, LANE_BLOCK, stream, c, a);
       }
-      if (mode == I2C_BWD_CHUNKED) return backward_chunked(p, c, a, ms, fuse, stream, false);
       if (!a.xm || !a.cell_stats) return I2C_EINVAL;  // two-pass needs both as workspace
-      ScanArgs<R, S> sc{a.fwd, const_cast<S*>(a.xm), (R*)p->temp, a.status};
-      int rc = launch(k_scan<M, R, S>, p->B, 1, LANE_BLOCK, stream, c, sc);
+      const ScanArgs<R, S> sc{a.fwd, const_cast<S*>(a.xm), (R*)p->temp, a.status};
+      rc = launch(k_scan<M, R, S>, p->B, 1, LANE_BLOCK, stream, c, sc);
       if (rc == I2C_OK) rc = launch(k_cell<M, R, S>, p->B, p->T, CELL_BLOCK, stream, c, a);
       if (rc == I2C_OK) rc = launch_reduce<M, R>(c, a, ms, p->T, stream);
       if (fuse) fuse->done = true;
-      return rc;
     }
-    return I2C_ENOTSUP;
+    return rc;
+  }
+  // The chunked schedule for every rule: compose (one lane per trajectory and chunk) -> stitch -> walk -> reduce. Sigma-point rule: each
+  // of the first three passes on the lane kernels or in the quad form (four trajectories per wavefront), as the plan says. Linearize
+  // and Gauss-Hermite (fp64 storage): the lane kernels, with their own stitch and walk -- the composition of the x-marginal recursion
+  // has no transform in it --, and Linearize its own reduction over the chunks' partial sums.
+  static int backward_chunked(const I2cProblem* p, const Plan& pl, const C& c, const CellArgs<R, S>& a, const MstepArgs<R>& ms, MstepFuse* fuse,
+                              void* stream) {
+    int rc = I2C_ENOTSUP;
+    if constexpr (LANE) {
+      const ChunkArgs<R, S> ch = chunk_args<M>(p, a);
+      const long B = p->B;
+      const int nc = ch.n_chunks;
+      const bool lin = !MIXED && pl.rule == I2C_INF_LINEARIZE, gh = !MIXED && pl.rule == I2C_INF_GAUSS_HERMITE;
+      if (fuse) fuse->done = true;  // the M-step rides on this schedule's reduction (set whether or not a pass fails to launch)
+      // compose
+      if (pl.compose == I2C_FAMILY_QUAD) {
+        if constexpr (QUAD8) rc = launch_quad_chunk_compose<M, R, S>(c, ch, stream);
+      } else {
+        rc = launch(k_chunk_compose<M, R, S>, B, nc, LANE_BLOCK, stream, c, ch);
+      }
+      if (rc != I2C_OK) return rc;
+      // stitch
+      rc = I2C_ENOTSUP;
+      if (pl.stitch == I2C_FAMILY_QUAD) {
+        if constexpr (QUAD8) rc = launch_quad_chunk_stitch<M, R, S>(c, ch, stream);
+      } else if (lin || gh) {
+        if constexpr (!MIXED)
+          rc = lin ? launch(k_chunk_stitch_lin<M, R>, B, 1, LANE_BLOCK, stream, c, ch) : launch(k_chunk_stitch<M, R, R, true>, B, 1, LANE_BLOCK, stream, c, ch);
+      } else {
+        rc = launch(k_chunk_stitch<M, R, S>, B, 1, LANE_BLOCK, stream, c, ch);
+      }
+      if (rc != I2C_OK) return rc;
+      // walk
+      rc = I2C_ENOTSUP;
+      if (pl.walker == I2C_FAMILY_QUAD) {
+        if constexpr (QUAD8) rc = launch_quad_chunk_walk<M, R, S>(c, ch, stream);
+      } else if (lin || gh) {
+        if constexpr (!MIXED)
+          rc = lin ? launch(k_chunk_walk_lin<M, R>, B, nc, LANE_BLOCK, stream, c, ch) : launch(k_chunk_walk<M, R, R, false, true>, B, nc, LANE_BLOCK, stream, c, ch);
+      } else {
+        const bool lean = I2C_WALK_LEAN && !a.xm && !a.zpost && !a.cell_stats && !c.z_per_cell;  // see chunk_walk_body
+        rc = lean ? launch(k_chunk_walk<M, R, S, true>, B, nc, LANE_BLOCK, stream, c, ch) : launch(k_chunk_walk<M, R, S>, B, nc, LANE_BLOCK, stream, c, ch);
+      }
+      if (rc != I2C_OK) return rc;
+      // reduce
+      if (lin) {
+        if constexpr (!MIXED) rc = launch(k_chunk_reduce_lin<M, R>, B, 1, LANE_BLOCK, stream, c, ch, ms);
+      } else {
+        C cr = c;  // reduction over chunks instead of cells: same kernel, T := number of chunks
+        cr.T = nc;
+        CellArgs<R, S> ared = a;
+        ared.cell_stats = ch.part;
+        rc = launch_reduce<M, R>(cr, ared, ms, p->T, stream);
+      }
+    }
+    return rc;
+  }
+  static int backward(const I2cProblem* p, const void* fwd, void* xm, void* post, void* zpost, void* cell_stats,
+                      void* term_stats, int32_t* status, void* stream) {
+    return run_backward(p, resolve(p), make_consts<M, R>(p, 0.0, 0), fwd, xm, post, zpost, cell_stats, term_stats, status, stream, nullptr);
   }
 
   static int riccati(const I2cProblem* p, const void* prior_out, const void* fwd, const void* xm, void* post, void* ric,
                      int32_t* status, void* stream) {
     if constexpr (MIXED) return I2C_ENOTSUP;
     if constexpr (LANE) {
-      if (use_group(p) != 0) return I2C_ENOTSUP;
+      if (!lane_request(p->group_lanes)) return I2C_ENOTSUP;
       const C c = make_consts<M, R>(p, 0.0, 0);
       RiccatiArgs<R> a{(const R*)prior_out, (const R*)fwd, (const R*)xm, (const R*)p->z, (const R*)p->alpha,
                        (R*)post,            (R*)ric,       status};
@@ -1428,11 +1400,13 @@ template <class M, typename R, typename S = R> struct Impl {
     return I2C_ENOTSUP;
   }
 
-  static int mstep(const I2cProblem* p, const void* term_stats, double tol, int update, void* stats_out,
-                   void* stream) {
-    const C c = make_consts<M, R>(p, tol, 0);
+  // `c`: the constants of the call with the M-step's tolerance
+  static int run_mstep(const I2cProblem* p, const C& c, const void* term_stats, int update, void* stats_out, void* stream) {
     MstepArgs<R> a{(const R*)term_stats, (R*)p->alpha, (R*)stats_out, update};
     return launch(k_mstep<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
+  }
+  static int mstep(const I2cProblem* p, const void* term_stats, double tol, int update, void* stats_out, void* stream) {
+    return run_mstep(p, make_consts<M, R>(p, tol, 0), term_stats, update, stats_out, stream);
   }
 
   // _update_priors (i2c.py:1210-1213): cells with index <= tau switch to feedback mode
@@ -1444,107 +1418,94 @@ template <class M, typename R, typename S = R> struct Impl {
   static int learn(const I2cProblem* p, void* post, void* fwd, void* xm, void* zpost, void* cell_stats,
                    void* term_stats, double tol, int tau, int n_iters, void* stats_hist, int32_t* status,
                    void* stream) {
+    const Plan pl = resolve(p);
+    const C cf = forward_consts(p), cb = make_consts<M, R>(p, tol, 0);
     for (int it = 0; it < n_iters; ++it) {
-      int rc = forward(p, post, fwd, nullptr, status, stream);
+      void* stats = (R*)stats_hist + (size_t)it * 4 * p->B;
+      MstepFuse fuse{tol, 1, stats, false};
+      int rc = run_forward(p, pl, cf, post, fwd, nullptr, status, stream);
+      if (rc == I2C_OK) rc = run_backward(p, pl, cb, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, &fuse);
+      if (rc == I2C_OK && !fuse.done) rc = run_mstep(p, cb, term_stats, 1, stats, stream);  // fused / group / Linearize / Gauss-Hermite walks have no reduction kernel
+      if (rc == I2C_OK && tau > 0 && it == 0) rc = to_feedback(p, tau, stream);  // idempotent: once per call
       if (rc != I2C_OK) return rc;
-      MstepFuse fuse{tol, 1, (R*)stats_hist + (size_t)it * 4 * p->B, false};
-      rc = backward_impl(p, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, &fuse);
-      if (rc != I2C_OK) return rc;
-      if (!fuse.done) {  // fused / group / Linearize / Gauss-Hermite schedules have no reduction kernel
-        rc = mstep(p, term_stats, tol, 1, (R*)stats_hist + (size_t)it * 4 * p->B, stream);
-        if (rc != I2C_OK) return rc;
-      }
-      if (tau > 0 && it == 0) {  // idempotent: once per call
-        rc = to_feedback(p, tau, stream);
-        if (rc != I2C_OK) return rc;
-      }
     }
     return I2C_OK;
   }
 
   // n_iters EM iterations WITH closed-loop propagation (covariance control: learn_msgs with _propagate, i2c.py:1238-1251) enqueued by
   // one call: forward, backward, propagate, M-step per iteration. From the second iteration on the propagation of iteration k
-  // shares a launch with the forward sweep of iteration k + 1 (k_forward_propagate) where both run on the lane kernels; the
-  // first one runs in order -- its M-step is followed by the mode-flag switch the propagation reads. Same kernels' bodies, same
+  // shares a launch with the forward sweep of iteration k + 1 (k_forward_propagate) where both run on the lane kernels (Plan::fusable);
+  // the first one runs in order -- its M-step is followed by the mode-flag switch the propagation reads. Same kernels' bodies, same
   // inputs as the one-by-one calls: identical results (a trajectory that fails in BOTH overlapped sweeps records either code).
   static int learn_propagate(const I2cProblem* p, void* post, void* fwd, void* xm, void* zpost, void* cell_stats, void* term_stats,
                              void* prop, void* prop_hist, double tol, int tau, int n_iters, void* stats_hist, int use_expert,
                              int overlap, int32_t* status, void* stream) {
     if constexpr (MIXED) return I2C_ENOTSUP;
+    const Plan pl = resolve(p);
+    const C cf = forward_consts(p), cb = make_consts<M, R>(p, tol, 0), cp = propagate_consts(p, use_expert);
     auto prop_row = [&](int it) { return (void*)((R*)prop_hist + (size_t)it * 3 * p->B); };
-    bool fusable = false;
-    if constexpr (LANE && C::D <= 5) {
-      const C c0 = make_consts<M, R>(p, 0.0, use_expert);
-      fusable = overlap && p->inference == I2C_INF_CUBATURE && family(p, c0, I2C_SWEEP_FORWARD) == I2C_FAMILY_LANE &&
-                family(p, c0, I2C_SWEEP_PROPAGATE) == I2C_FAMILY_LANE && c0.rule_xu.unit && c0.rule_x.unit && !c0.z_per_cell &&
-                !p->alpha_cell && c0.t0 == 0;
-    }
     int pending = -1;  // iteration whose propagation has not run yet
     for (int it = 0; it < n_iters; ++it) {
       int rc = I2C_OK;
       bool fused = false;
       if constexpr (LANE && C::D <= 5) {
-        if (fusable && pending >= 0) {
-          const C c = make_consts<M, R>(p, 0.0, use_expert);
+        if (overlap && pl.fusable && pending >= 0) {  // (fusable: the sigma-point rule as given, so cp is the forward sweep's constants with use_expert)
           FwdArgs<R> af{(const R*)post, (R*)fwd, nullptr, (const R*)p->x0, (const R*)p->sig_x0, (const R*)p->z, (const R*)p->alpha,
                         (const R*)p->alpha_cell, p->feedforward, status, p->expert};
           PropArgs<R> ap{(const R*)post, (R*)prop, (R*)prop_row(pending), (const R*)p->x0, (const R*)p->sig_x0,
                          (const R*)p->z, p->feedforward, status, p->expert};
-          rc = launch(k_forward_propagate<M, R, true>, p->B, 2, LANE_BLOCK, stream, c, af, ap);
+          rc = launch(k_forward_propagate<M, R, true>, p->B, 2, LANE_BLOCK, stream, cp, af, ap);
           fused = true;
           pending = -1;
         }
       }
       if (!fused) {
         if (pending >= 0) {
-          rc = propagate(p, post, prop, prop_row(pending), use_expert, status, stream);
+          rc = run_propagate(p, pl, cp, post, prop, prop_row(pending), status, stream);
           pending = -1;
           if (rc != I2C_OK) return rc;
         }
-        rc = forward(p, post, fwd, nullptr, status, stream);
+        rc = run_forward(p, pl, cf, post, fwd, nullptr, status, stream);
       }
       if (rc != I2C_OK) return rc;
-      MstepFuse fuse{tol, 1, (R*)stats_hist + (size_t)it * 4 * p->B, false};
-      rc = backward_impl(p, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, &fuse);
+      void* stats = (R*)stats_hist + (size_t)it * 4 * p->B;
+      MstepFuse fuse{tol, 1, stats, false};
+      rc = run_backward(p, pl, cb, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, &fuse);
       if (rc != I2C_OK) return rc;
       if (it == 0) {  // in order: the mode flags change right after this M-step
-        rc = propagate(p, post, prop, prop_row(0), use_expert, status, stream);
+        rc = run_propagate(p, pl, cp, post, prop, prop_row(0), status, stream);
         if (rc != I2C_OK) return rc;
       } else {
         pending = it;
       }
-      if (!fuse.done) {
-        rc = mstep(p, term_stats, tol, 1, (R*)stats_hist + (size_t)it * 4 * p->B, stream);
-        if (rc != I2C_OK) return rc;
-      }
-      if (tau > 0 && it == 0) {
-        rc = to_feedback(p, tau, stream);
-        if (rc != I2C_OK) return rc;
-      }
+      if (!fuse.done) rc = run_mstep(p, cb, term_stats, 1, stats, stream);
+      if (rc == I2C_OK && tau > 0 && it == 0) rc = to_feedback(p, tau, stream);
+      if (rc != I2C_OK) return rc;
     }
-    if (pending >= 0) return propagate(p, post, prop, prop_row(pending), use_expert, status, stream);
+    if (pending >= 0) return run_propagate(p, pl, cp, post, prop, prop_row(pending), status, stream);
     return I2C_OK;
   }
 
-  static int ckf(const I2cProblem* p, const double* sig_zeta, const void* y, const void* u, void* mu, void* cov,
-                 int32_t* status, void* stream) {
-    if constexpr (MIXED) return I2C_ENOTSUP;
-    const I2cProblem q = filter_problem(p);
-    p = &q;
-    const C c = make_consts<M, R>(p, 0.0, 0);
+  static int run_ckf(const I2cProblem* p, const Plan& pl, const double* sig_zeta, const void* y, const void* u, void* mu, void* cov,
+                     int32_t* status, void* stream) {
+    if (pl.filter < 0) return pl.filter;
+    const C c = filter_consts(p);
     ZetaArg<M, R> z;
     for (int i = 0; i < sym(M::NY); ++i) z.v[i] = (R)sig_zeta[i];
     CkfArgs<R> a{(const R*)y, (const R*)u, (R*)mu, (R*)cov, status};
-    const int fam = family(p, c, I2C_SWEEP_FILTER);
-    if (fam < 0) return fam;
-    if (fam == I2C_FAMILY_QUAD) {
+    if (pl.filter == I2C_FAMILY_QUAD) {
       if constexpr (HAS_QUAD_CKF) return launch_quad_ckf<M, R>(c, z, a, stream);
     }
-    if (fam == I2C_FAMILY_GROUP) {
+    if (pl.filter == I2C_FAMILY_GROUP) {
       if constexpr (HAS_GROUP) return launch_group<GK_CKF, M, R, G>(c, &z, a, stream);
     }
     if constexpr (LANE) return launch(k_ckf<M, R>, p->B, 1, LANE_BLOCK, stream, c, z, a);
     return I2C_ENOTSUP;
+  }
+  static int ckf(const I2cProblem* p, const double* sig_zeta, const void* y, const void* u, void* mu, void* cov,
+                 int32_t* status, void* stream) {
+    if constexpr (MIXED) return I2C_ENOTSUP;
+    return run_ckf(p, resolve(p), sig_zeta, y, u, mu, cov, status, stream);
   }
 
   // One control step of the MPC loop enqueued by one call (i2c/policy/mpc.py:156-182): filter, n_iter x (forward,
@@ -1552,21 +1513,26 @@ template <class M, typename R, typename S = R> struct Impl {
   // (the caller then advances I2cProblem.t0 by one and moves terminal_cell).
   static int mpc_step(const I2cProblem* p, const I2cMpcStep* m, void* stream) {
     if constexpr (MIXED) return I2C_ENOTSUP;
+    const Plan pl = resolve(p);
+    const C cf = forward_consts(p), cb = make_consts<M, R>(p, 0.0, 0);
     int rc = I2C_OK;
-    if (m->do_filter) rc = ckf(p, m->sig_zeta, m->y, m->u, const_cast<void*>(p->x0), const_cast<void*>(p->sig_x0), m->status, stream);
+    if (m->do_filter) rc = run_ckf(p, pl, m->sig_zeta, m->y, m->u, const_cast<void*>(p->x0), const_cast<void*>(p->sig_x0), m->status, stream);
     for (int it = 0; it < m->n_iter && rc == I2C_OK; ++it) {
-      rc = forward(p, m->post, m->fwd, nullptr, m->status, stream);
-      if (rc == I2C_OK) rc = backward(p, m->fwd, m->xm, m->post, m->zpost, m->cell_stats, m->term_stats, m->status, stream);
+      rc = run_forward(p, pl, cf, m->post, m->fwd, nullptr, m->status, stream);
+      if (rc == I2C_OK) rc = run_backward(p, pl, cb, m->fwd, m->xm, m->post, m->zpost, m->cell_stats, m->term_stats, m->status, stream, nullptr);
       if (rc == I2C_OK && m->tau > 0 && it == 0) rc = to_feedback(p, m->tau, stream);  // (idempotent within a step: _update_priors)
     }
     if (rc != I2C_OK) return rc;
-    return shift(p, m->post, m->cell_init, m->alpha_init, m->z_new, m->action, stream);
+    return run_shift(p, cb, m->post, m->cell_init, m->alpha_init, m->z_new, m->action, stream);
   }
   // the receding-horizon shift alone (BatchedI2c.shift_horizon, the step-by-step path of the policies)
   static int shift(const I2cProblem* p, void* post, const void* cell_init, const void* alpha_init, const void* z_new, void* action,
                    void* stream) {
     if constexpr (MIXED) return I2C_ENOTSUP;
-    const C c = make_consts<M, R>(p, 0.0, 0);
+    return run_shift(p, make_consts<M, R>(p, 0.0, 0), post, cell_init, alpha_init, z_new, action, stream);
+  }
+  static int run_shift(const I2cProblem* p, const C& c, void* post, const void* cell_init, const void* alpha_init, const void* z_new,
+                       void* action, void* stream) {
     ShiftArgs<R> a{(R*)post, (const R*)cell_init, (R*)const_cast<void*>(p->alpha_cell), (const R*)alpha_init,
                    (R*)const_cast<void*>(p->z_per_cell ? p->z : nullptr), (const R*)z_new, const_cast<uint8_t*>(p->feedforward),
                    (R*)action};
@@ -1603,33 +1569,31 @@ template <class M, typename R, typename S = R> struct Impl {
     return launch(k_plant_step<M, R>, p->B, 1, LANE_BLOCK, stream, c, nz, a);
   }
 
-  static int propagate(const I2cProblem* p, const void* post, void* prop, void* prop_stats, int use_expert,
-                       int32_t* status, void* stream) {
-    if constexpr (MIXED) return I2C_ENOTSUP;
-    // under Linearize() the closed-loop propagation IS CubatureQuadrature(1, 0, 0) whatever the caller left in the quad fields
-    // (i2c.py:109-115), like the state estimator's rule (filter_problem)
-    I2cProblem q = *p;
-    if (p->inference == I2C_INF_LINEARIZE) q.quad_alpha = 1.0, q.quad_beta = 0.0, q.quad_kappa = 0.0;
-    p = &q;
-    const C c = make_consts<M, R>(p, 0.0, use_expert);
+  // `c`: propagate_consts
+  static int run_propagate(const I2cProblem* p, const Plan& pl, const C& c, const void* post, void* prop, void* prop_stats, int32_t* status,
+                           void* stream) {
+    if (pl.propagate < 0) return pl.propagate;
     PropArgs<R> a{(const R*)post, (R*)prop, (R*)prop_stats, (const R*)p->x0, (const R*)p->sig_x0,
                   (const R*)p->z, p->feedforward, status, p->expert};
-    const int fam = family(p, c, I2C_SWEEP_PROPAGATE);
-    if (fam < 0) return fam;
-    if (fam == I2C_FAMILY_QUAD) {
+    if (pl.propagate == I2C_FAMILY_QUAD) {
       if constexpr (HAS_QUAD_PROP) return launch_quad_propagate<M, R>(c, a, stream);
     }
-    if (fam == I2C_FAMILY_GROUP) {
+    if (pl.propagate == I2C_FAMILY_GROUP) {
       if constexpr (HAS_GROUP) return launch_group<GK_PROPAGATE, M, R, G>(c, nullptr, a, stream);
     }
-    if (fam == I2C_FAMILY_GRID) {
+    if (pl.propagate == I2C_FAMILY_GRID) {
       if constexpr (HAS_GRID) return launch_grid<GRK_PROPAGATE, M, R>(c, a, stream);
     }
     if constexpr (LANE) {
-      if (p->inference == I2C_INF_GAUSS_HERMITE) return launch(k_propagate<M, R, true>, p->B, 1, LANE_BLOCK, stream, c, a);
+      if (pl.rule == I2C_INF_GAUSS_HERMITE) return launch(k_propagate<M, R, true>, p->B, 1, LANE_BLOCK, stream, c, a);
       return launch(k_propagate<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
     }
     return I2C_ENOTSUP;
+  }
+  static int propagate(const I2cProblem* p, const void* post, void* prop, void* prop_stats, int use_expert,
+                       int32_t* status, void* stream) {
+    if constexpr (MIXED) return I2C_ENOTSUP;
+    return run_propagate(p, resolve(p), propagate_consts(p, use_expert), post, prop, prop_stats, status, stream);
   }
 };
 

@@ -61,7 +61,7 @@ struct Pendulum {
   // (-DI2C_PENDULUM_GROUP=8 through I2C_HIPCC_EXTRA): the shipped build is 4, the widest group with a row for every lane but one.
   static constexpr int GROUP = I2C_PENDULUM_GROUP;
   static constexpr bool GROUP_ONLY = false;
-  static constexpr bool GROUP_FORWARD_AUTO = false;  // see Impl::forward_any (i2c_impl.hpp)
+  static constexpr bool GROUP_FORWARD_AUTO = false;  // see Impl::lane_or_group (i2c_impl.hpp)
   static constexpr bool WAVE = false;  // one-wavefront-per-trajectory kernels (i2c_wave.hpp): d = 16 models only
   static constexpr bool QUAD = true;  // four-trajectories-per-wavefront forward kernel (i2c_quad.hpp): d <= 8 models
   static constexpr int QUAD_FORWARD_MAX_B = 0;  // the quad kernel is the DEFAULT forward sweep up to this batch size (measured crossover, profiles/README.md); 0: only on request
@@ -109,7 +109,7 @@ struct PendulumActReg {
   static constexpr int ID = 1, NX = 2, NU = 1, NZ = 1, NZT = 0, NP = 0, NA = 1;
   static constexpr int GROUP = 4;  // lanes per trajectory of the group kernels (i2c_group.hpp); 0: none compiled
   static constexpr bool GROUP_ONLY = false;
-  static constexpr bool GROUP_FORWARD_AUTO = false;  // see Impl::forward_any (i2c_impl.hpp)
+  static constexpr bool GROUP_FORWARD_AUTO = false;  // see Impl::lane_or_group (i2c_impl.hpp)
   static constexpr bool WAVE = false;  // one-wavefront-per-trajectory kernels (i2c_wave.hpp): d = 16 models only
   static constexpr bool QUAD = true;  // four-trajectories-per-wavefront forward kernel (i2c_quad.hpp): d <= 8 models
   static constexpr int QUAD_FORWARD_MAX_B = 0;  // the quad kernel is the DEFAULT forward sweep up to this batch size (measured crossover, profiles/README.md); 0: only on request
@@ -138,7 +138,7 @@ struct Cartpole {
   static constexpr int ID = 2, NX = 4, NU = 1, NZ = 6, NZT = 5, NP = 0, NA = 1;
   static constexpr int GROUP = 8;  // lanes per trajectory of the group kernels (i2c_group.hpp); 0: none compiled
   static constexpr bool GROUP_ONLY = false;
-  static constexpr bool GROUP_FORWARD_AUTO = false;  // see Impl::forward_any (i2c_impl.hpp)
+  static constexpr bool GROUP_FORWARD_AUTO = false;  // see Impl::lane_or_group (i2c_impl.hpp)
   static constexpr bool WAVE = false;  // one-wavefront-per-trajectory kernels (i2c_wave.hpp): d = 16 models only
   static constexpr bool QUAD = true;  // four-trajectories-per-wavefront forward kernel (i2c_quad.hpp): d <= 8 models
   static constexpr int QUAD_FORWARD_MAX_B = 4096;  // the quad kernel is the DEFAULT forward sweep up to this batch size (measured crossover, profiles/README.md); 0: only on request
@@ -197,7 +197,7 @@ struct DoubleCartpole {
   static constexpr int ID = 3, NX = 6, NU = 1, NZ = 9, NZT = 8, NP = 0, NA = 2;
   static constexpr int GROUP = 16;  // lanes per trajectory of the group kernels (i2c_group.hpp); 0: none compiled
   static constexpr bool GROUP_ONLY = false;
-  static constexpr bool GROUP_FORWARD_AUTO = true;   // see Impl::forward_any (i2c_impl.hpp)
+  static constexpr bool GROUP_FORWARD_AUTO = true;   // see Impl::lane_or_group (i2c_impl.hpp)
   static constexpr bool WAVE = false;  // one-wavefront-per-trajectory kernels (i2c_wave.hpp): d = 16 models only
   static constexpr bool QUAD = true;  // four-trajectories-per-wavefront forward kernel (i2c_quad.hpp): d <= 8 models
   static constexpr int QUAD_FORWARD_MAX_B = 8192;  // the quad kernel is the DEFAULT forward sweep up to this batch size (measured crossover, profiles/README.md); 0: only on request
@@ -283,7 +283,7 @@ struct Linear {
   static constexpr int ID = 4, NX = 2, NU = 1, NZ = 3, NZT = 2, NP = 8, NA = 0;
   static constexpr int GROUP = 4;  // lanes per trajectory of the group kernels (i2c_group.hpp); 0: none compiled
   static constexpr bool GROUP_ONLY = false;
-  static constexpr bool GROUP_FORWARD_AUTO = false;  // see Impl::forward_any (i2c_impl.hpp)
+  static constexpr bool GROUP_FORWARD_AUTO = false;  // see Impl::lane_or_group (i2c_impl.hpp)
   static constexpr bool WAVE = false;  // one-wavefront-per-trajectory kernels (i2c_wave.hpp): d = 16 models only
   static constexpr bool QUAD = true;  // four-trajectories-per-wavefront forward kernel (i2c_quad.hpp): d <= 8 models
   static constexpr int QUAD_FORWARD_MAX_B = 0;  // the quad kernel is the DEFAULT forward sweep up to this batch size (measured crossover, profiles/README.md); 0: only on request
@@ -321,7 +321,7 @@ struct LinearMinEnergy {
   static constexpr int ID = 5, NX = 2, NU = 1, NZ = 1, NZT = 2, NP = 8, NA = 0;
   static constexpr int GROUP = 0;  // lanes per trajectory of the group kernels (i2c_group.hpp); 0: none compiled
   static constexpr bool GROUP_ONLY = false;
-  static constexpr bool GROUP_FORWARD_AUTO = false;  // see Impl::forward_any (i2c_impl.hpp)
+  static constexpr bool GROUP_FORWARD_AUTO = false;  // see Impl::lane_or_group (i2c_impl.hpp)
   static constexpr bool WAVE = false;  // one-wavefront-per-trajectory kernels (i2c_wave.hpp): d = 16 models only
   static constexpr bool QUAD = true;  // four-trajectories-per-wavefront forward kernel (i2c_quad.hpp): d <= 8 models
   static constexpr int QUAD_FORWARD_MAX_B = 0;  // the quad kernel is the DEFAULT forward sweep up to this batch size (measured crossover, profiles/README.md); 0: only on request
@@ -360,7 +360,7 @@ struct Quadrotor {
   static constexpr int ID = 6, NX = 6, NU = 2, NZ = 8, NZT = 6, NP = 3, NA = 1;
   static constexpr int GROUP = 8;  // lanes per trajectory of the group kernels (i2c_group.hpp); 0: none compiled
   static constexpr bool GROUP_ONLY = false;
-  static constexpr bool GROUP_FORWARD_AUTO = true;   // see Impl::forward_any (i2c_impl.hpp)
+  static constexpr bool GROUP_FORWARD_AUTO = true;   // see Impl::lane_or_group (i2c_impl.hpp)
   static constexpr bool WAVE = false;  // one-wavefront-per-trajectory kernels (i2c_wave.hpp): d = 16 models only
   static constexpr bool QUAD = true;  // four-trajectories-per-wavefront forward kernel (i2c_quad.hpp): d <= 8 models
   static constexpr int QUAD_FORWARD_MAX_B = 8192;  // the quad kernel is the DEFAULT forward sweep up to this batch size (measured crossover, profiles/README.md); 0: only on request

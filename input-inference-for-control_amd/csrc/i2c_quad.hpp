@@ -2516,7 +2516,7 @@ I2C_HD inline void compose_quad8_body(const Consts<M, R>& c, const S* fwd, R* co
 // points through the dynamics with the applied action appended (mpc.py:129-137), chol of the prediction, the points through
 // sys.measure, Kalman update on the measurement (mpc.py:139-145). With it a control step of the 12-state quadrotor (filter +
 // sweeps, i2c_mpc_step) runs on matrix-instruction kernels end to end; the estimator's rule is CubatureQuadrature(1, 0, 0)
-// whatever the graph infers with (mpc.py:121-123: Impl::filter_problem), so the unit-weight forms of q_moments always apply.
+// whatever the graph infers with (mpc.py:121-123: Impl::filter_consts), so the unit-weight forms of q_moments always apply.
 template <class M, typename R> struct QKConst {
   static constexpr int QLD = QG<M>::QLD;
   R eta[QLD * QLD], zeta[QLD * QLD];  // sig_eta (nx x nx), sig_zeta (ny x ny), zero-padded

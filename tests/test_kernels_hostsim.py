@@ -86,7 +86,7 @@ def test_hostsim_quad12_both_families_vs_reference_golden(lib, name, lanes):
 @pytest.mark.parametrize("mode", ["fused", "two_pass"])
 def test_hostsim_wave_backward_schedules_vs_reference_golden(lib, mode):
     """The wave family's two backward schedules -- the fused walk, and the sequential nx x nx scan + one wave per (t, b) cell +
-    reduction (on request only: measured slower on the device, see Impl::schedule) -- against the same golden run."""
+    reduction (on request only: measured slower on the device, see Impl::lane_schedule) -- against the same golden run."""
     eng = parity.check_against_golden("em_quad12_T20", lib, "cpu", 1e-7, 1e-6, n_iters=4, group_lanes=64, backward_mode=mode)
     assert eng.backward_schedule == mode and eng.backward_family == "wave"
 
