@@ -2,7 +2,7 @@
 python tools/ab_bitexact.py <other_lib.so> [model] [B] [group_lanes] [T] [inference] [storage]
 group_lanes: a kernel-family request, e.g. 64 = the wave / quad kernels, 16 = the group kernels of the 12-state quadrotor; default 0 =
 what the model runs by default ("G": the model's group width). T: default the horizon of the model's config. inference: cubature
-(default) | linearize | gauss_hermite (degree 3, degree 2 for d > 5). storage: fp64 (default) | fp32 (fp64 arithmetic on fp32-stored messages). B, group_lanes, T,
+(default) | linearize | gauss_hermite (degree 3, degree 2 for d > 5). storage: fp64 (default) | fp32 (fp64 arithmetic on fp32-stored messages) | f32a (fp32 ARITHMETIC and storage). B, group_lanes, T,
 inference and storage each take a comma-separated list: every combination runs in this one process. A request the engine refuses
 prints one "refused" line. Exit status 1 if any line differs; the last line counts lines, refusals and differences.
 I2C_AB_LIB=<lib.so>: the library compared against (default: the in-tree build); I2C_AB_NO_WORK=1: run without the chunk workspace;
@@ -48,7 +48,7 @@ gh_degree = 3 if model.dim_x + nu <= 5 else 2  # (a grid of at most 256 points p
 
 
 def run(lib, mode, B, lanes, T, inference, storage, x0, mu_u):
-    extra = {"storage_dtype": torch.float32} if storage == "fp32" else {}
+    extra = {"storage_dtype": torch.float32} if storage == "fp32" else {"dtype": torch.float32, "allow_inexact": True} if storage == "f32a" else {}
     if os.environ.get("I2C_AB_PER_TRAJ"):  # the per-trajectory-parameter tables, every trajectory with the model's own parameters
         extra["model_params"] = np.tile(np.asarray(model.device_params(), float), (B, 1))
     eng = pkg.BatchedI2c(model, T, cfg["Q"], cfg["R"], cfg.get("Qf", cfg["Q"]), cfg["alpha"], cfg["tol"], mu_u, cfg["sig_u"] * np.eye(nu),
