@@ -1623,6 +1623,26 @@ I2C_HD inline void chunk_compose_body(const Consts<M, R>& c, const ChunkArgs<R, 
   for (int i = 0; i < sym(NX); ++i) out[(long)(NX + NX * NX + i) * B] = Cc[i];
 }
 
+// One step of the stitch recursion: the smoothed state (m, S) that enters a chunk pushed through that chunk's composite map,
+//   m <- a + G m,  S <- C + G S G^T   (Cc is overwritten).
+// Written once for the stitch pass and for the self-stitching walker (chunk_boundary_state): the same expressions in the same order
+// from the same start, so the boundary states of the two are bit-identical.
+template <int NX, typename R> I2C_FN void apply_composite(const R* av, const R* G, R* Cc, R* m, R* S) {
+  R mn[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) {
+    R v = av[i];
+#pragma unroll
+    for (int k = 0; k < NX; ++k) v += G[i * NX + k] * m[k];
+    mn[i] = v;
+  }
+  add_JDJt<NX, NX>(G, S, Cc);  // C + G S G^T
+#pragma unroll
+  for (int i = 0; i < NX; ++i) m[i] = mn[i];
+#pragma unroll
+  for (int i = 0; i < sym(NX); ++i) S[i] = Cc[i];
+}
+
 template <class M, typename R, typename S_ = R, int GRID = 0>
 I2C_HD inline void chunk_stitch_body(const Consts<M, R>& c, const ChunkArgs<R, S_>& a, const int b) {
   using C = Consts<M, R>;
@@ -1655,19 +1675,7 @@ I2C_HD inline void chunk_stitch_body(const Consts<M, R>& c, const ChunkArgs<R, S
     for (int i = 0; i < NX; ++i) bo[(long)i * B] = m[i];
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) bo[(long)(NX + i) * B] = S[i];
-    R mn[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-      R v = av[i];
-#pragma unroll
-      for (int k = 0; k < NX; ++k) v += G[i * NX + k] * m[k];
-      mn[i] = v;
-    }
-    add_JDJt<NX, NX>(G, S, Cc);  // C + G S G^T
-#pragma unroll
-    for (int i = 0; i < NX; ++i) m[i] = mn[i];
-#pragma unroll
-    for (int i = 0; i < sym(NX); ++i) S[i] = Cc[i];
+    apply_composite<NX, R>(av, G, Cc, m, S);
 #pragma unroll
     for (int i = 0; i < NX; ++i) av[i] = nav[i];
 #pragma unroll
@@ -1677,12 +1685,48 @@ I2C_HD inline void chunk_stitch_body(const Consts<M, R>& c, const ChunkArgs<R, S
   }
 }
 
+// The self-stitching walker's boundary state: the smoothed state entering chunk `ch`, recomputed by that chunk's walker instead of
+// read from `bnd` -- the terminal filtered state pushed through the composites of chunks NC-1 .. ch+1, which is what chunk_stitch_body
+// stores into bnd[ch]. The stitch pass (a launch and a chain of NC dependent load round trips on B / 64 waves) then does not run.
+// Only for problems WITHOUT a terminal state prior: there end_of_chain is the identity on the filtered state (with one it advances
+// temp[b], once per trajectory -- several walkers per trajectory would race; Impl::backward_chunked keeps those on the stitch pass).
+// The composites are fetched DEPTH at a time, all loads of a batch issued before its first application (one round trip per batch:
+// NC <= 16 is one batch for nx = 2); a walker whose suffix is shorter re-reads the composite nearest to it instead (same cache line).
+template <class M, typename R, typename S_>
+I2C_FN void chunk_boundary_state(const Consts<M, R>& c, const ChunkArgs<R, S_>& a, const int ch, const int b, R* m, R* S) {
+  using C = Consts<M, R>;
+  constexpr int NX = C::NX, D = C::D;
+  constexpr int O_MU3 = D + sym(D), O_S3 = O_MU3 + NX, EC = NX + NX * NX + sym(NX);
+  constexpr int DEPTH = NX <= 2 ? 8 : 4;
+  const long B = c.B;
+  const S_* last = a.cell.fwd + ((long)(c.T - 1) * C::E_FWD) * B + b;
+#pragma unroll
+  for (int i = 0; i < NX; ++i) m[i] = last[(long)(O_MU3 + i) * B];
+#pragma unroll
+  for (int i = 0; i < sym(NX); ++i) S[i] = last[(long)(O_S3 + i) * B];
+  for (int hi = a.n_chunks - 1; hi > ch; hi -= DEPTH) {
+    R comp[DEPTH][EC];
+#pragma unroll
+    for (int k = 0; k < DEPTH; ++k) {
+      const R* cp = a.comp + ((long)(hi - k > ch ? hi - k : ch + 1) * EC) * B + b;
+#pragma unroll
+      for (int i = 0; i < EC; ++i) comp[k][i] = cp[(long)i * B];
+    }
+#pragma unroll
+    for (int k = 0; k < DEPTH; ++k)
+      if (hi - k > ch) apply_composite<NX, R>(comp[k], comp[k] + NX, comp[k] + NX + NX * NX, m, S);
+  }
+}
+
 // LEANW: the common case fixed at compile time (no smoothed-state / observed-marginal / per-cell-cost outputs, one shared target):
 // with the optional stores behind run-time branches the compiler cannot count the memory operations between the row prefetch and
 // its use, so its s_waitcnt at the top of a cell also waits for the PREVIOUS cell's stores to be acknowledged (vmcnt is one
 // in-order counter) -- 41 % of the walk's cycles (profiles/r3_pendulum_B4096_chunked_sq_summary.txt).
 // GRID: the Gauss-Hermite tensor-grid transform in the cell (GaussHermiteQuadrature: the chunked schedule of that rule)
-template <class M, typename R, typename S_ = R, bool LEANW = false, int GRID = 0>
+// SELF: the self-stitching form (sigma-point rule, no terminal state prior, d <= 5): the walker computes its own boundary state
+// (chunk_boundary_state) behind the prefetch of its first row, and the walker of the LAST chunk -- whose boundary state is the end of
+// the chain -- writes the terminal observation statistics, once per trajectory, as the stitch pass does in the four-pass schedule.
+template <class M, typename R, typename S_ = R, bool LEANW = false, int GRID = 0, bool SELF = false>
 I2C_HD inline void chunk_walk_body(const Consts<M, R>& c, const ChunkArgs<R, S_>& a, const int ch, const int b) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NZ = C::NZ, D = C::D;
@@ -1695,7 +1739,7 @@ I2C_HD inline void chunk_walk_body(const Consts<M, R>& c, const ChunkArgs<R, S_>
   if (LEANW) ca.xm = nullptr, ca.zpost = nullptr, ca.cell_stats = nullptr;
   const bool z_per_cell = LEANW ? false : c.z_per_cell != 0;
   R m3m[NX], S3m[sym(NX)];
-  {
+  if (!SELF) {
     const R* bi = a.bnd + ((long)ch * C::E_XM) * B + b;
 #pragma unroll
     for (int i = 0; i < NX; ++i) m3m[i] = bi[(long)i * B];
@@ -1725,6 +1769,11 @@ I2C_HD inline void chunk_walk_body(const Consts<M, R>& c, const ChunkArgs<R, S_>
     // settle them before the loop: the waitcnt pass joins the loop-entry state with the back-edge state, and loads still pending
     // on the entry path (youngest operations there, but older than a cell's stores on the back edge) make it wait for
     // vmcnt(0) -- the previous cell's stores -- at the top of EVERY cell (see forward_sweep_body)
+    if (SELF) {  // (younger than the row's loads in the in-order counter: the settling below covers them as well)
+      static_assert(!SELF || (GRID == 0 && DOUBLE_BUFFER), "the self-stitching walker: sigma-point rule, d <= 5");
+      chunk_boundary_state<M, R, S_>(c, a, ch, b, m3m, S3m);
+      if (ch == a.n_chunks - 1) terminal_obs_stats<M, R, GRID>(c, b, m3m, S3m, ca.term_stats, ca.status);
+    }
     if (LEANW) {
 #pragma unroll
       for (int e = 0; e < C::E_FWD; ++e) row[e] = opaque(row[e]);
@@ -1791,21 +1840,20 @@ template <typename R> struct MstepArgs {
   int update;
 };
 
+// The M-step on values: `stat`, `v`, `m` = the alpha statistic, the cost variance and the plan cost (term_stats rows 1, 2 and, under
+// Linearize, the last one), `trT` = the terminal statistic (row 0), `alpha` = the trajectory's temperature. mstep_body reads them
+// from term_stats; the prologue of k_forward_mstep (i2c_impl.hpp) has them in registers.
 template <class M, typename R>
-I2C_HD inline void mstep_body(const Consts<M, R>& c, const MstepArgs<R>& a, const int b) {
+I2C_FN void mstep_update(const Consts<M, R>& c, const MstepArgs<R>& a, const int b, const R trT, const R stat, const R v, const R m,
+                         const R alpha) {
   using C = Consts<M, R>;
   const long B = c.B;
-  // row 1 is the alpha statistic sum_t tr(QR (err err^T + sig_z0_m)); in the sigma-point path it IS the plan cost,
-  // the Linearize path reports the cost of the graph's cubature transform separately (last row)
-  const R stat = a.term_stats[B + b], v = a.term_stats[2 * B + b];
-  const R m = c.inference == I2C_INF_LINEARIZE ? a.term_stats[(long)(C::E_TERM - 1) * B + b] : stat;
   R tr = stat, sf = R(C::NZ) * R(c.T);
   if (C::NZT > 0 && c.has_Qf) {
-    tr += a.term_stats[b];
+    tr += trT;
     sf += R(C::NZT);
   }
   const R alpha_hat = tr / sf;
-  const R alpha = a.alpha[b];
   R alpha_new = alpha;
   if (a.update) {
     if (c.tol >= R(0)) {  // i2c.py:953-959
@@ -1820,6 +1868,17 @@ I2C_HD inline void mstep_body(const Consts<M, R>& c, const MstepArgs<R>& a, cons
   a.stats_out[B + b] = alpha_new;
   a.stats_out[2 * B + b] = m;
   a.stats_out[3 * B + b] = v;
+}
+template <class M, typename R>
+I2C_HD inline void mstep_body(const Consts<M, R>& c, const MstepArgs<R>& a, const int b) {
+  using C = Consts<M, R>;
+  const long B = c.B;
+  // row 1 is the alpha statistic sum_t tr(QR (err err^T + sig_z0_m)); in the sigma-point path it IS the plan cost,
+  // the Linearize path reports the cost of the graph's cubature transform separately (last row)
+  const R stat = a.term_stats[B + b], v = a.term_stats[2 * B + b];
+  const R m = c.inference == I2C_INF_LINEARIZE ? a.term_stats[(long)(C::E_TERM - 1) * B + b] : stat;
+  const R trT = (C::NZT > 0 && c.has_Qf) ? a.term_stats[b] : R(0);
+  mstep_update<M, R>(c, a, b, trT, stat, v, m, a.alpha[b]);
 }
 
 // ------------------------------------------------------------------------------------------

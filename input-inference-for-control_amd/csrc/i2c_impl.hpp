@@ -138,6 +138,12 @@ I2C_KERNEL(LANE_BLOCK) k_chunk_walk(I2C_LANE_PARAMS const Consts<M, R> c, const 
   const long b = I2C_LANE_X(LANE_BLOCK);
   if (b < c.B) chunk_walk_body<M, R, S, LEANW, GRID>(c, a, I2C_LANE_Y, (int)b);
 }
+// the self-stitching walker (chunk_walk_body<SELF>): the stitch pass's work in the prologue of the walk, d <= 5
+template <class M, typename R, typename S = R, bool LEANW = false>
+I2C_KERNEL(LANE_BLOCK) k_chunk_walk_self(I2C_LANE_PARAMS const Consts<M, R> c, const ChunkArgs<R, S> a) {
+  const long b = I2C_LANE_X(LANE_BLOCK);
+  if (b < c.B) chunk_walk_body<M, R, S, LEANW, 0, true>(c, a, I2C_LANE_Y, (int)b);
+}
 template <class M, typename R> I2C_KERNEL(LANE_BLOCK) k_chunk_stitch_lin(I2C_LANE_PARAMS const Consts<M, R> c, const ChunkArgs<R, R> a) {
   const long b = I2C_LANE_X(LANE_BLOCK);
   if (b < c.B) chunk_stitch_lin_body<M, R>(c, a, (int)b);
@@ -259,6 +265,72 @@ static int launch_reduce(const Consts<M, R>& c, const CA& a, const MstepArgs<R>&
   return hipGetLastError() == hipSuccess ? I2C_OK : I2C_ELAUNCH;
 }
 #endif
+
+// The reduction and M-step of one EM iteration finished by the NEXT iteration's forward sweep (i2c_learn behind a self-stitching
+// chunked backward sweep; Impl::learn): lane b of k_forward_mstep adds the walkers' partial sums part[NC][2][B] of its trajectory in
+// k_reduce's order, writes term_stats rows 1, 2 and runs the M-step (mstep_update) -- all before the sweep reads alpha[b], which that
+// M-step updates. The kernel boundary behind the walk gives the visibility; the lane reads and writes only its own trajectory's
+// elements, so nothing is exchanged between lanes. k_reduce -- a launch and a drain for O(NC) additions per trajectory -- then runs
+// once per i2c_learn call, after the last iteration.
+template <typename R> struct PendingMstep {
+  const R* part;     // [NC][2][B]: the walkers' cost sums
+  R* term_stats;     // [E_TERM][B]
+  MstepArgs<R> ms;   // alpha, the iteration's row of the statistics history
+  int n_chunks;
+  R tol;             // the M-step's tolerance (the forward sweep's constants carry none)
+};
+// The order of the additions is k_reduce's: its lane q adds the chunks q, q + REDUCE_PARTS, ... in ascending order (reduce_partial) --
+// accumulator q here --, then the partial sums are added in the order of q. At the head of a kernel every load is a round trip to
+// memory, so the prologue makes ONE: the temperature, the terminal statistic and 2 x REDUCE_PARTS chunks' sums are requested before
+// anything is stored (NC <= 16: all of them), and the M-step works on those registers instead of reading back what was just written.
+// A round that reaches past the last chunk re-reads it and adds +0 instead, which changes no accumulator (none of them can hold -0:
+// each starts from +0). Sigma-point rule only: the plan cost is the alpha statistic.
+template <class M, typename R> I2C_FN void finish_pending_mstep(const Consts<M, R>& c, const PendingMstep<R>& pm, const int b) {
+  using C = Consts<M, R>;
+  constexpr int P = REDUCE_PARTS;
+  const long B = c.B;
+  const int nc = pm.n_chunks;
+  const R alpha = pm.ms.alpha[b];
+  const R trT = (C::NZT > 0 && c.has_Qf) ? pm.term_stats[b] : R(0);
+  R sm[P], sv[P];
+#pragma unroll
+  for (int q = 0; q < P; ++q) sm[q] = sv[q] = R(0);
+  for (int t0 = 0; t0 < nc; t0 += 2 * P) {
+    R pm_t[2 * P], pv_t[2 * P];
+#pragma unroll
+    for (int i = 0; i < 2 * P; ++i) {
+      const long t = t0 + i < nc ? t0 + i : nc - 1;
+      pm_t[i] = pm.part[(t * 2 + 0) * B + b];
+      pv_t[i] = pm.part[(t * 2 + 1) * B + b];
+    }
+#pragma unroll
+    for (int i = 0; i < 2 * P; ++i) {
+      const bool in = t0 + i < nc;
+      sm[i % P] += in ? pm_t[i] : R(0);
+      sv[i % P] += in ? pv_t[i] : R(0);
+    }
+  }
+  R m = R(0), v = R(0);
+#pragma unroll
+  for (int q = 0; q < P; ++q) {
+    m += sm[q];
+    v += sv[q];
+  }
+  pm.term_stats[B + b] = m;  // (reduce_finish)
+  pm.term_stats[2 * B + b] = v;
+  Consts<M, R> cm = c;
+  cm.tol = pm.tol;
+  mstep_update<M, R>(cm, pm.ms, b, trT, m, v, m, alpha);
+}
+// (the time loop is forward_sweep_body's own: the prologue sits in front of it, outside)
+template <class M, typename R, bool LEAN, typename S = R>
+I2C_KERNEL(LANE_BLOCK) k_forward_mstep(I2C_LANE_PARAMS const Consts<M, R> c, const FwdArgs<R, S> a, const int block, const PendingMstep<R> pm) {
+  const long b = I2C_LANE_X(block);
+  if (b < c.B) {
+    finish_pending_mstep<M, R>(c, pm, (int)b);
+    forward_sweep_body<M, R, LEAN, 0, S>(c, a, (int)b);
+  }
+}
 
 // ---- the ONE place that knows how a multi-lane body runs -----------------------------------------------------------------------
 // The group, wave and quad kernels run a body as a TEAM of lanes (G, 64, 64) that share an LDS region and exchange values across lanes.
@@ -818,6 +890,13 @@ static void chunk_geometry(int B, int T, int* n_chunks, int* chunk_len) {
   *chunk_len = len;
   *n_chunks = (T + len - 1) / len;
 }
+// Experiment knob (not part of the ABI), read on EVERY backward call: I2C_CHUNK_PASSES=4 runs the chunked schedule as its four passes
+// compose -> stitch -> walk -> reduce wherever the two-launch form (self-stitching walker, deferred reduction) would run: the
+// reference of that form's tests and of its A/B timing.
+static bool chunk_four_passes() {
+  const char* e = getenv("I2C_CHUNK_PASSES");
+  return e && atoi(e) == 4;
+}
 // The workspace of the chunked schedules (I2cProblem.work), as element offsets: the composite maps [NC][NX + NX*NX + sym(NX)][B] at 0,
 // behind them the smoothed states entering the chunks [NC][NX + sym(NX)][B] and the per-chunk cost sums [NC][3][B]
 template <class M> struct ChunkWork {
@@ -1216,9 +1295,11 @@ template <class M, typename R, typename S = R> struct Impl {
   }
 
   // ---- the sweeps: each written once for either storage type, dispatched from the plan --------------------------------------------
+  // `pend` (i2c_learn only, see defers_mstep): the previous iteration's reduction and M-step, finished in this sweep's prologue
   static int run_forward(const I2cProblem* p, const Plan& pl, const C& c, const void* prior, void* fwd, void* prior_out, int32_t* status,
-                         void* stream) {
+                         void* stream, const PendingMstep<R>* pend = nullptr) {
     if (pl.forward < 0) return pl.forward;
+    if (pend && !defers_mstep(pl)) return I2C_EINVAL;  // (only the lane sweep below has the prologue)
     const FwdArgs<R, S> a{(const S*)prior, (S*)fwd, (S*)prior_out, (const R*)p->x0, (const R*)p->sig_x0,
                           (const R*)p->z,  (const R*)p->alpha, (const R*)p->alpha_cell, p->feedforward, status, p->expert};
     if (pl.forward == I2C_FAMILY_WAVE) {
@@ -1248,6 +1329,10 @@ template <class M, typename R, typename S = R> struct Impl {
       const int lanes = sweep_lanes();
 #endif
       const bool lean = c.rule_xu.unit && c.rule_x.unit && !c.z_per_cell && !a.alpha_cell && !a.prior_out && c.t0 == 0;
+      if constexpr (SELF_STITCH) {
+        if (pend) return lean ? launch(k_forward_mstep<M, R, true, S>, p->B, 1, lanes, stream, c, a, lanes, *pend)
+                              : launch(k_forward_mstep<M, R, false, S>, p->B, 1, lanes, stream, c, a, lanes, *pend);
+      }
       if (lean) return launch(k_forward<M, R, true, false, S>, p->B, 1, lanes, stream, c, a, lanes);
       return launch(k_forward<M, R, false, false, S>, p->B, 1, lanes, stream, c, a, lanes);
     }
@@ -1263,7 +1348,20 @@ template <class M, typename R, typename S = R> struct Impl {
     int update;
     void* stats_out;
     bool done;
+    bool defer;               // in: the caller's next forward sweep can finish the reduction and the M-step (defers_mstep)
+    bool deferred;            // out: it has to -- the schedule did not launch its reduction --,
+    PendingMstep<R> pending;  //      with these arguments
   };
+  // The two-launch form of the chunked schedule (compose, self-stitching walk) exists for the d <= 5 lane models ...
+  static constexpr bool SELF_STITCH = LANE && C::D <= 5;
+  // ... and runs under the sigma-point rule with lane stitch and walk passes, for problems without a terminal state prior (whose end
+  // of the chain advances temp[b]: once per trajectory, so not by several walkers)
+  static bool self_stitches(const Plan& pl, const C& c) {
+    return SELF_STITCH && pl.rule == I2C_INF_CUBATURE && pl.stitch == I2C_FAMILY_LANE && pl.walker == I2C_FAMILY_LANE && !c.has_x_terminal &&
+           !chunk_four_passes();
+  }
+  // i2c_learn: the forward sweep of the next iteration is the lane k_forward, which has the variant with the M-step prologue
+  static bool defers_mstep(const Plan& pl) { return SELF_STITCH && pl.rule == I2C_INF_CUBATURE && pl.forward == I2C_FAMILY_LANE; }
   // Linearize() applies the terminal cost at the END of the chain, with the temperature of the cell that sits there
   // (i2c.py:475-491: the cell's own sig_xi_terminal). A receding-horizon loop appends cells that keep the temperature they were
   // copied with (I2cProblem.alpha_cell), so after the first shift that is not the graph's alpha.
@@ -1326,7 +1424,8 @@ template <class M, typename R, typename S = R> struct Impl {
     }
     return rc;
   }
-  // The chunked schedule for every rule: compose (one lane per trajectory and chunk) -> stitch -> walk -> reduce. Sigma-point rule: each
+  // The chunked schedule for every rule: compose (one lane per trajectory and chunk) -> stitch -> walk -> reduce; in the two-launch form
+  // (self_stitches) compose -> self-stitching walk, then the reduction, unless i2c_learn's next forward sweep takes it. Sigma-point rule: each
   // of the first three passes on the lane kernels or in the quad form (four trajectories per wavefront), as the plan says. Linearize
   // and Gauss-Hermite (fp64 storage): the lane kernels, with their own stitch and walk -- the composition of the x-marginal recursion
   // has no transform in it --, and Linearize its own reduction over the chunks' partial sums.
@@ -1338,6 +1437,7 @@ template <class M, typename R, typename S = R> struct Impl {
       const long B = p->B;
       const int nc = ch.n_chunks;
       const bool lin = !MIXED && pl.rule == I2C_INF_LINEARIZE, gh = !MIXED && pl.rule == I2C_INF_GAUSS_HERMITE;
+      const bool self = self_stitches(pl, c);
       if (fuse) fuse->done = true;  // the M-step rides on this schedule's reduction (set whether or not a pass fails to launch)
       // compose
       if (pl.compose == I2C_FAMILY_QUAD) {
@@ -1353,8 +1453,10 @@ template <class M, typename R, typename S = R> struct Impl {
       } else if (lin || gh) {
         if constexpr (!MIXED)
           rc = lin ? launch(k_chunk_stitch_lin<M, R>, B, 1, LANE_BLOCK, stream, c, ch) : launch(k_chunk_stitch<M, R, R, true>, B, 1, LANE_BLOCK, stream, c, ch);
-      } else {
+      } else if (!self) {
         rc = launch(k_chunk_stitch<M, R, S>, B, 1, LANE_BLOCK, stream, c, ch);
+      } else {
+        rc = I2C_OK;  // (the walkers compute their boundary states themselves; `bnd` stays unused)
       }
       if (rc != I2C_OK) return rc;
       // walk
@@ -1366,12 +1468,20 @@ template <class M, typename R, typename S = R> struct Impl {
           rc = lin ? launch(k_chunk_walk_lin<M, R>, B, nc, LANE_BLOCK, stream, c, ch) : launch(k_chunk_walk<M, R, R, false, true>, B, nc, LANE_BLOCK, stream, c, ch);
       } else {
         const bool lean = I2C_WALK_LEAN && !a.xm && !a.zpost && !a.cell_stats && !c.z_per_cell;  // see chunk_walk_body
-        rc = lean ? launch(k_chunk_walk<M, R, S, true>, B, nc, LANE_BLOCK, stream, c, ch) : launch(k_chunk_walk<M, R, S>, B, nc, LANE_BLOCK, stream, c, ch);
+        if constexpr (SELF_STITCH) {
+          if (self)
+            rc = lean ? launch(k_chunk_walk_self<M, R, S, true>, B, nc, LANE_BLOCK, stream, c, ch)
+                      : launch(k_chunk_walk_self<M, R, S>, B, nc, LANE_BLOCK, stream, c, ch);
+        }
+        if (!self) rc = lean ? launch(k_chunk_walk<M, R, S, true>, B, nc, LANE_BLOCK, stream, c, ch) : launch(k_chunk_walk<M, R, S>, B, nc, LANE_BLOCK, stream, c, ch);
       }
       if (rc != I2C_OK) return rc;
       // reduce
       if (lin) {
         if constexpr (!MIXED) rc = launch(k_chunk_reduce_lin<M, R>, B, 1, LANE_BLOCK, stream, c, ch, ms);
+      } else if (self && fuse && fuse->defer) {  // finish_pending_mstep, in the prologue of the caller's next forward sweep
+        fuse->deferred = true;
+        fuse->pending = PendingMstep<R>{ch.part, a.term_stats, ms, nc, c.tol};
       } else {
         C cr = c;  // reduction over chunks instead of cells: same kernel, T := number of chunks
         cr.T = nc;
@@ -1420,11 +1530,17 @@ template <class M, typename R, typename S = R> struct Impl {
                    void* stream) {
     const Plan pl = resolve(p);
     const C cf = forward_consts(p), cb = make_consts<M, R>(p, tol, 0);
+    // Behind a self-stitching chunked backward sweep the reduction and the M-step of iteration `it` run in the prologue of iteration
+    // it + 1's forward sweep (k_forward_mstep); the last iteration of the call ends with k_reduce as a backward sweep on its own does.
+    PendingMstep<R> pend{};
+    bool have_pend = false;
     for (int it = 0; it < n_iters; ++it) {
       void* stats = (R*)stats_hist + (size_t)it * 4 * p->B;
-      MstepFuse fuse{tol, 1, stats, false};
-      int rc = run_forward(p, pl, cf, post, fwd, nullptr, status, stream);
+      MstepFuse fuse{tol, 1, stats, false, it + 1 < n_iters && defers_mstep(pl), false, {}};
+      int rc = run_forward(p, pl, cf, post, fwd, nullptr, status, stream, have_pend ? &pend : nullptr);
+      have_pend = false;
       if (rc == I2C_OK) rc = run_backward(p, pl, cb, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, &fuse);
+      if (rc == I2C_OK && fuse.deferred) pend = fuse.pending, have_pend = true;
       if (rc == I2C_OK && !fuse.done) rc = run_mstep(p, cb, term_stats, 1, stats, stream);  // fused / group / Linearize / Gauss-Hermite walks have no reduction kernel
       if (rc == I2C_OK && tau > 0 && it == 0) rc = to_feedback(p, tau, stream);  // idempotent: once per call
       if (rc != I2C_OK) return rc;
