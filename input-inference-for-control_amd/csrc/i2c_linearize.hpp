@@ -57,6 +57,16 @@ template <class M, int FN, typename T> I2C_FN void call_model(const T* p, const 
   if (FN == FN_OBSERVE_TERMINAL) M::observe_terminal(p, x, sn, cs, y);
 }
 
+// OPTIONAL member of a functor: value and Jacobian of one callback in one evaluation, common subexpressions shared
+//   template <int FN, typename R> I2C_FN void jacobian(const R* p, const R* x, const R* sn, const R* cs, R* y, R* Jac);  // Jac[k * DIN + j]
+// (functor_codegen.py emits it for a model written in Python; no hand-written functor has it). Detected, never required:
+template <class M, int FN, typename R, typename = void> struct has_jacobian : std::false_type {};
+template <class M, int FN, typename R>
+struct has_jacobian<M, FN, R, std::void_t<decltype(M::template jacobian<FN, R>((const R*)nullptr, (const R*)nullptr, (const R*)nullptr,
+                                                                                 (const R*)nullptr, (R*)nullptr, (R*)nullptr))>> : std::true_type {};
+// ... whose derivative of clip is that of r_clip(Dual): 1 strictly inside the limits, 0 on and outside them
+template <typename R> I2C_FN R r_clip_grad(R x, R lo, R hi) { return (x > lo && x < hi) ? R(1) : R(0); }
+
 // y = f(m) and Jac[k * DIN + j] = d y_k / d m_j for one of the model callbacks (parameters: params_of(), i2c_cell.hpp).
 template <class M, int FN, int DIN, int DOUT, typename R>
 I2C_FN void value_and_jacobian(const R* params, const R* m, R* y, R* Jac) {
@@ -64,6 +74,10 @@ I2C_FN void value_and_jacobian(const R* params, const R* m, R* y, R* Jac) {
   R sn[NA], cs[NA];
 #pragma unroll
   for (int a = 0; a < M::NA; ++a) r_sincos(m[M::ang(a)], &sn[a], &cs[a]);
+  if constexpr (has_jacobian<M, FN, R>::value) {
+    M::template jacobian<FN, R>(params, m, sn, cs, y, Jac);
+    return;
+  }
   call_model<M, FN, R>(params, m, sn, cs, y);
   Dual<R> pd[NP1];
 #pragma unroll

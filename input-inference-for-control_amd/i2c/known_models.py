@@ -74,7 +74,8 @@ class KnownModel:
             return int(self.model_id)
         if self.hip_header is None:
             raise TypeError(f"{type(self).__name__}: a model needs a compiled-in model_id or a hip_header with its device functor "
-                            "(arbitrary Python callables cannot run inside the kernels; INTEGRATION.md section 3)")
+                            "(arbitrary Python callables cannot run inside the kernels; INTEGRATION.md section 3), or to be a "
+                            "TracedModel, whose Python functions are traced into one (i2c.traced_model, INTEGRATION.md section 3b)")
         ids = lib.__dict__.setdefault("_plugin_ids", {})
         key = (os.path.abspath(self.hip_header), self.hip_struct, self.hip_name)
         if key not in ids:
@@ -586,6 +587,15 @@ ENVIRONMENTS = {
     "PlanarQuadrotor": PlanarQuadrotor,
     "Quadrotor12": Quadrotor12,
 }
+
+
+def __getattr__(name):
+    # TracedModel (i2c/traced_model.py derives it from KnownModel, so it is imported on first use, not at the top)
+    if name == "TracedModel":
+        from .traced_model import TracedModel
+
+        return TracedModel
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def make_env_model(env_def, model_def=None):
