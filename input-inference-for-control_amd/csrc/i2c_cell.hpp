@@ -698,11 +698,52 @@ template <typename R, typename S = R> struct FwdArgs {
   const uint8_t* expert;  // [T] ring or null: per-cell use_expert_controller (Linearize forward only, i2c.py:259-265)
 };
 
+// REL: what the sweep does when a chunk of the chunked backward schedule has all its forward messages in memory. NoRelease: nothing
+// (every kernel but one). ChunkRelease (k_forward_helper, i2c_impl.hpp): the sweep shares its workgroup with a second wavefront that
+// composes the finished chunks; release() makes this wave's stores visible to it and meets it at the workgroup barrier. The sweep
+// calls release() once per chunk -- n_chunks times whatever happens to a trajectory (failures are branch-free) --, the helper waits
+// at the barrier as many times: no wave ever waits on memory contents.
+// Inside the cell the test `t == at` and the release are ONE statement without control flow the compiler can see: a branch there
+// splits the cell's basic block, and a product and its sum on different sides of the split are no longer contracted into the same
+// fused multiply-add -- the sweep would round differently from k_forward (measured: two fma fewer per cell, posterior off in the last
+// bits). The wait for this wave's stores (vmcnt(0)) is the release; "memory" keeps the compiler's accesses on their side of it.
+// That is enough where the waves of a workgroup share one CU and its vector L1 (the default; the kernel is NOT built for threadgroup-
+// split mode, where the two waves could sit on different CUs and the release would have to write back / invalidate as well).
+// The contraction is the compiler's choice: the device cases of tests/test_forward_helper.py (torch.equal against k_forward) are what
+// holds it across compiler versions.
+struct NoRelease {
+  static constexpr bool ON = false;
+  int chunk_len;
+  I2C_HD inline void release() const {}
+  I2C_HD inline void release_if(int, int) const {}
+};
+struct ChunkRelease {
+  static constexpr bool ON = true;
+  int chunk_len;  // ChunkArgs::chunk_len, wave-uniform
+  I2C_HD inline void release() const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), whatever the target's memory model asks of a workgroup-scope fence
+    __builtin_amdgcn_s_barrier();
+#endif
+  }
+  I2C_HD inline void release_if(const int t, const int at) const {  // t, at: wave-uniform
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_cmp_lg_u32 %0, %1\n\ts_cbranch_scc1 .Lnot_released_%=\n\ts_waitcnt vmcnt(0)\n\ts_barrier\n.Lnot_released_%=:"
+                 :
+                 : "s"(t), "s"(at)
+                 : "memory", "scc");
+#else
+    (void)t, (void)at;
+#endif
+  }
+};
+
 // LEAN = the common case fixed at compile time (weights sum to 1, shared target, trajectory-level alpha, no
 // joint-prior output): the corresponding wave-uniform runtime branches disappear from the cell, which keeps
 // it one scheduling region. The generic variant (LEAN = false) handles everything.
-template <class M, typename R, bool LEAN = false, int GRID = 0, typename ST_ = R>
-I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST_>& a, const int b) {
+template <class M, typename R, bool LEAN = false, int GRID = 0, typename ST_ = R, class REL = NoRelease>
+I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST_>& a, const int b, const REL rel = REL{0}) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NU = C::NU, NZ = C::NZ, NZT = C::NZT, D = C::D;
   constexpr unsigned W = sizeof(ST_);
@@ -794,6 +835,7 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
     for (int i = 0; i < sym(NX); ++i) eta_v[i] = opaque(LEAN ? c.sig_eta[i] : c.sig_eta_w[i]);
   }
 
+  [[maybe_unused]] int next_release = rel.chunk_len;  // (REL) the first cell of the second chunk
   for (int t = 0; t < T; ++t) {
     const int tn = t + 1 < T ? t + 1 : t;
     const int tr = LEAN ? t : c.row(t), tnr = LEAN ? tn : c.row(tn);  // rows of the persistent buffers (ring, see Consts::t0)
@@ -975,6 +1017,13 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
 #pragma unroll
       for (int e = 0; e < C::E_PRI; ++e) pri[e] = opaque(pri[e]);
     }
+    // The first cell of a chunk releases the PREVIOUS chunk (REL above): here every store of the previous cell is older than loads
+    // that have returned, and this cell's own (mu0, S0) were issued a dynamics transform ago -- the wait inside release() finds
+    // nothing outstanding. (At the end of the chunk's own last cell it would wait for that cell's store acknowledgements.)
+    if constexpr (REL::ON) {
+      rel.release_if(t, next_release);
+      next_release += t == next_release ? rel.chunk_len : 0;
+    }
     // J is written out BEFORE the terminal update so that its d*nx registers are dead there (with J
     // live the terminal block is the register peak of the large models and spills to scratch)
     if (wr) {
@@ -1010,6 +1059,7 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
     }
 
   }
+  if constexpr (REL::ON) rel.release();  // the last chunk
   if (wr && fail != 0 && a.status[b] == 0) a.status[b] = fail;
 }
 

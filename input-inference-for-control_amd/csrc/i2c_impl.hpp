@@ -22,6 +22,7 @@
 #include "i2c_linearize.hpp"
 
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -331,6 +332,52 @@ I2C_KERNEL(LANE_BLOCK) k_forward_mstep(I2C_LANE_PARAMS const Consts<M, R> c, con
     forward_sweep_body<M, R, LEAN, 0, S>(c, a, (int)b);
   }
 }
+
+// The forward sweep of i2c_learn with a HELPER wavefront (Impl::forward_helper_on): a workgroup of two waves over the same 64
+// trajectories. Wave 0 is k_forward / k_forward_mstep and releases every chunk of the chunked backward schedule once its messages are
+// stored (ChunkRelease, i2c_cell.hpp); wave 1 -- on another SIMD of the same CU, so it takes no issue slot from the chain -- waits at
+// the workgroup barrier and then composes that chunk with chunk_compose_body, unchanged: the composites are k_chunk_compose's bit
+// for bit, and the backward sweep that follows starts with its walk. Both waves take the chunk geometry from the same argument and
+// meet at the barrier n_chunks times; nothing is exchanged through flags in memory. (Every wave has a live lane: the grid covers B.)
+// Host simulation: a lane's sweep, then its chunks -- a valid schedule, compose reads only finished rows.
+template <class M, typename R, bool LEAN, typename S, bool MSTEP>
+I2C_FN void forward_helper_lane(const Consts<M, R>& c, const FwdArgs<R, S>& a, const ChunkArgs<R, S>& ch, const PendingMstep<R>& pm,
+                                const int role, const int b) {
+  if (role == 0) {
+    if constexpr (MSTEP) finish_pending_mstep<M, R>(c, pm, b);
+    forward_sweep_body<M, R, LEAN, 0, S, ChunkRelease>(c, a, b, ChunkRelease{ch.chunk_len});
+  } else {
+    for (int k = 0; k < ch.n_chunks; ++k) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#endif
+      chunk_compose_body<M, R, S>(c, ch, k, b);
+    }
+  }
+}
+#ifdef I2C_HOST_SIM
+constexpr int HELPER_WAVES = 1;  // (lanes per trajectory that launch() loops over)
+#define I2C_HELPER_LANES                                                                \
+  const long b = I2C_LANE_X(LANE_BLOCK);                                                \
+  for (int role = 0; role < 2; ++role)
+#else
+constexpr int HELPER_WAVES = 2;
+#define I2C_HELPER_LANES                                                                \
+  const long b = (long)blockIdx.x * LANE_BLOCK + (threadIdx.x & (LANE_BLOCK - 1));      \
+  const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / LANE_BLOCK));     \
+  if (b < c.B)
+#endif
+template <class M, typename R, bool LEAN, typename S = R>
+I2C_KERNEL(2 * LANE_BLOCK) k_forward_helper(I2C_LANE_PARAMS const Consts<M, R> c, const FwdArgs<R, S> a, const ChunkArgs<R, S> ch) {
+  I2C_HELPER_LANES forward_helper_lane<M, R, LEAN, S, false>(c, a, ch, PendingMstep<R>{}, role, (int)b);
+}
+template <class M, typename R, bool LEAN, typename S = R>
+I2C_KERNEL(2 * LANE_BLOCK) k_forward_mstep_helper(I2C_LANE_PARAMS const Consts<M, R> c, const FwdArgs<R, S> a, const ChunkArgs<R, S> ch,
+                                                  const PendingMstep<R> pm) {
+  I2C_HELPER_LANES forward_helper_lane<M, R, LEAN, S, true>(c, a, ch, pm, role, (int)b);
+}
+#undef I2C_HELPER_LANES
 
 // ---- the ONE place that knows how a multi-lane body runs -----------------------------------------------------------------------
 // The group, wave and quad kernels run a body as a TEAM of lanes (G, 64, 64) that share an LDS region and exchange values across lanes.
@@ -897,6 +944,14 @@ static bool chunk_four_passes() {
   const char* e = getenv("I2C_CHUNK_PASSES");
   return e && atoi(e) == 4;
 }
+// Diagnostic knob (not part of the ABI), read where it reports: I2C_TRACE_PLAN=1 writes to stderr what a call dispatches beyond what
+// the plan's exports report -- at the launch of a lane forward sweep "i2c_forward_lane: sweep=<helper|plain>", in the chunked schedule
+// "i2c_backward_chunked: compose=<skipped|launched>" (tests/test_forward_helper.py reads them: the helper wave's composites and a
+// compose launch's are the same bytes in the same place).
+static bool plan_trace() {
+  const char* e = getenv("I2C_TRACE_PLAN");
+  return e && atoi(e) == 1;
+}
 // The workspace of the chunked schedules (I2cProblem.work), as element offsets: the composite maps [NC][NX + NX*NX + sym(NX)][B] at 0,
 // behind them the smoothed states entering the chunks [NC][NX + sym(NX)][B] and the per-chunk cost sums [NC][3][B]
 template <class M> struct ChunkWork {
@@ -931,6 +986,9 @@ template <class M, typename R, typename S> static ChunkArgs<R, S> chunk_args(con
   template <class M> struct name<M, std::void_t<decltype(M::MEMBER)>> : std::integral_constant<int, M::MEMBER> {};
 // batch size from which I2C_BWD_AUTO runs the fused walk: the model's own measured crossover, or the library-wide default
 I2C_MODEL_CONST(bwd_fused_min_b, BWD_FUSED_MIN_B, I2C_BWD_FUSED_MIN_B)
+// batch size from which the forward sweep of i2c_learn composes the chunks on a helper wave (Impl::forward_helper_on); see
+// ModelDefaults (i2c_models.hpp) for the measurement behind the default
+I2C_MODEL_CONST(forward_helper_min_b, FORWARD_HELPER_MIN_B, 4096)
 // batch window in which the d <= 8 quad backward sweep is the model's DEFAULT; models without the pair: on request only
 I2C_MODEL_CONST(quad_backward_min_b, QUAD_BACKWARD8_MIN_B, 0)
 I2C_MODEL_CONST(quad_backward_max_b, QUAD_BACKWARD8_MAX_B, -1)
@@ -1296,8 +1354,9 @@ template <class M, typename R, typename S = R> struct Impl {
 
   // ---- the sweeps: each written once for either storage type, dispatched from the plan --------------------------------------------
   // `pend` (i2c_learn only, see defers_mstep): the previous iteration's reduction and M-step, finished in this sweep's prologue
+  // `helper` (i2c_learn only, see forward_helper_on): the chunks of the backward sweep that follows, composed beside this sweep
   static int run_forward(const I2cProblem* p, const Plan& pl, const C& c, const void* prior, void* fwd, void* prior_out, int32_t* status,
-                         void* stream, const PendingMstep<R>* pend = nullptr) {
+                         void* stream, const PendingMstep<R>* pend = nullptr, const ChunkArgs<R, S>* helper = nullptr) {
     if (pl.forward < 0) return pl.forward;
     if (pend && !defers_mstep(pl)) return I2C_EINVAL;  // (only the lane sweep below has the prologue)
     const FwdArgs<R, S> a{(const S*)prior, (S*)fwd, (S*)prior_out, (const R*)p->x0, (const R*)p->sig_x0,
@@ -1329,6 +1388,16 @@ template <class M, typename R, typename S = R> struct Impl {
       const int lanes = sweep_lanes();
 #endif
       const bool lean = c.rule_xu.unit && c.rule_x.unit && !c.z_per_cell && !a.alpha_cell && !a.prior_out && c.t0 == 0;
+      if (plan_trace()) fprintf(stderr, "i2c_forward_lane: sweep=%s\n", SELF_STITCH && helper ? "helper" : "plain");
+      if constexpr (SELF_STITCH) {
+        if (helper) {  // (forward_helper_on) two waves per workgroup: the sweep, and the compose pass of the backward sweep behind it
+          constexpr int W = HELPER_WAVES;
+          if (pend) return lean ? launch(k_forward_mstep_helper<M, R, true, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, *helper, *pend)
+                                : launch(k_forward_mstep_helper<M, R, false, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, *helper, *pend);
+          return lean ? launch(k_forward_helper<M, R, true, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, *helper)
+                      : launch(k_forward_helper<M, R, false, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, *helper);
+        }
+      }
       if constexpr (SELF_STITCH) {
         if (pend) return lean ? launch(k_forward_mstep<M, R, true, S>, p->B, 1, lanes, stream, c, a, lanes, *pend)
                               : launch(k_forward_mstep<M, R, false, S>, p->B, 1, lanes, stream, c, a, lanes, *pend);
@@ -1351,7 +1420,32 @@ template <class M, typename R, typename S = R> struct Impl {
     bool defer;               // in: the caller's next forward sweep can finish the reduction and the M-step (defers_mstep)
     bool deferred;            // out: it has to -- the schedule did not launch its reduction --,
     PendingMstep<R> pending;  //      with these arguments
+    bool composed;            // in: the caller's forward sweep has composed the chunks (forward_helper_on): the schedule starts behind its compose pass
   };
+  // Experiment knob (not part of the ABI), read on EVERY i2c_learn call: I2C_FORWARD_HELPER=0 brings back the forward sweep without
+  // the helper wave and the compose launch of the backward sweep -- the reference of tests/test_forward_helper.py and of the A/B
+  // timing --, as does I2C_CHUNK_PASSES=4 (the reference of tests/test_chunk_self_stitch.py stays as it was); any other value runs the
+  // helper at every batch size its window allows, below the model's forward_helper_min_b too. -1: not set.
+  static int forward_helper_knob() {
+    const char* e = getenv("I2C_FORWARD_HELPER");
+    if (chunk_four_passes() || (e && strcmp(e, "0") == 0)) return 0;
+    return e ? 1 : -1;
+  }
+  // i2c_learn: the forward sweep composes the chunks of the backward sweep behind it on a second wave (k_forward_helper) where that
+  // sweep is known to be this plan's chunked schedule with a lane compose pass over an existing workspace, and the forward sweep the
+  // lane kernel of a d <= 5 model under the sigma-point rule, 64 lanes to a wave, from the batch size at which it pays
+  // (forward_helper_min_b: short chunks leave the helper no more time to compose a chunk than the sweep takes to produce the next).
+  // A terminal state prior keeps the four passes.
+  static bool forward_helper_on(const I2cProblem* p, const Plan& pl, const C& c) {
+#ifndef I2C_HOST_SIM
+    if (sweep_lanes() != LANE_BLOCK) return false;
+#endif
+    const int knob = forward_helper_knob();
+    if (knob == 0 || (knob < 0 && p->B < forward_helper_min_b<M>::value)) return false;
+    const bool to_chunked = pl.backward == I2C_FAMILY_LANE || (QUAD8 && pl.backward == I2C_FAMILY_QUAD);  // run_backward's own test
+    return SELF_STITCH && LANE_BLOCK == 64 && pl.forward == I2C_FAMILY_LANE && pl.rule == I2C_INF_CUBATURE && to_chunked &&
+           schedule_with(pl, p->work != nullptr) == I2C_BWD_CHUNKED && pl.compose == I2C_FAMILY_LANE && !c.has_x_terminal;
+  }
   // The two-launch form of the chunked schedule (compose, self-stitching walk) exists for the d <= 5 lane models ...
   static constexpr bool SELF_STITCH = LANE && C::D <= 5;
   // ... and runs under the sigma-point rule with lane stitch and walk passes, for problems without a terminal state prior (whose end
@@ -1440,7 +1534,11 @@ template <class M, typename R, typename S = R> struct Impl {
       const bool self = self_stitches(pl, c);
       if (fuse) fuse->done = true;  // the M-step rides on this schedule's reduction (set whether or not a pass fails to launch)
       // compose
-      if (pl.compose == I2C_FAMILY_QUAD) {
+      const bool composed = fuse && fuse->composed;  // (the helper wave of the caller's forward sweep has written the composites)
+      if (plan_trace()) fprintf(stderr, "i2c_backward_chunked: compose=%s\n", composed ? "skipped" : "launched");
+      if (composed) {
+        rc = I2C_OK;
+      } else if (pl.compose == I2C_FAMILY_QUAD) {
         if constexpr (QUAD8) rc = launch_quad_chunk_compose<M, R, S>(c, ch, stream);
       } else {
         rc = launch(k_chunk_compose<M, R, S>, B, nc, LANE_BLOCK, stream, c, ch);
@@ -1534,10 +1632,16 @@ template <class M, typename R, typename S = R> struct Impl {
     // it + 1's forward sweep (k_forward_mstep); the last iteration of the call ends with k_reduce as a backward sweep on its own does.
     PendingMstep<R> pend{};
     bool have_pend = false;
+    // Every forward sweep of the call is followed by this plan's backward sweep: where that is the chunked schedule, the sweep's
+    // helper wave composes its chunks (forward_helper_on) and the schedule starts with its walk.
+    const bool helper = forward_helper_on(p, pl, cf);
+    CellArgs<R, S> of_fwd{};  // (the compose pass reads the forward messages only)
+    of_fwd.fwd = (const S*)fwd;
+    const ChunkArgs<R, S> chunks = helper ? chunk_args<M>(p, of_fwd) : ChunkArgs<R, S>{};
     for (int it = 0; it < n_iters; ++it) {
       void* stats = (R*)stats_hist + (size_t)it * 4 * p->B;
-      MstepFuse fuse{tol, 1, stats, false, it + 1 < n_iters && defers_mstep(pl), false, {}};
-      int rc = run_forward(p, pl, cf, post, fwd, nullptr, status, stream, have_pend ? &pend : nullptr);
+      MstepFuse fuse{tol, 1, stats, false, it + 1 < n_iters && defers_mstep(pl), false, {}, helper};
+      int rc = run_forward(p, pl, cf, post, fwd, nullptr, status, stream, have_pend ? &pend : nullptr, helper ? &chunks : nullptr);
       have_pend = false;
       if (rc == I2C_OK) rc = run_backward(p, pl, cb, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, &fuse);
       if (rc == I2C_OK && fuse.deferred) pend = fuse.pending, have_pend = true;

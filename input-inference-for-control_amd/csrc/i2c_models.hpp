@@ -42,6 +42,11 @@ struct ModelDefaults {
   static constexpr int QUAD_BACKWARD_MIN_B = 0;
   // (optional) static constexpr int BWD_FUSED_MIN_B: batch size from which I2C_BWD_AUTO runs the fused backward walk instead of the
   // chunked schedule; models without it take I2C_BWD_FUSED_MIN_B (include/i2c_hip.h)
+  // (optional) static constexpr int FORWARD_HELPER_MIN_B: batch size from which the lane forward sweep of i2c_learn composes the chunks
+  // of the backward sweep on a helper wave (k_forward_helper, i2c_impl.hpp); models without it take 4096. Measured on the pendulum,
+  // T = 200 (profiles/forward_helper_other_legs.txt): B = 4096 (16 chunks of 13 cells) 0.3458 -> 0.3394 ms per iteration; B = 1024
+  // (29 chunks of 7) 0.3170 -> 0.3177; B = 1 0.3531 -> 0.3694, T = 100 (25 chunks of 4) 0.1831 -> 0.1901: with chunks that short
+  // the sweep waits for the helper at the barrier. Not measured between 1024 and 4096, nor from 4097 to the fused walk's batch.
   I2C_HD static constexpr int ang(int) { return 0; }
   // structure hints of the observation functions (ObsStruct, i2c_cell.hpp): output k is a pass-through of input obs_lin(k), or
   // (-1) a general function that depends on no input with an index above obs_dep(k). The defaults say "nothing is known"
