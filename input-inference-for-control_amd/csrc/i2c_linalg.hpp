@@ -29,11 +29,20 @@ constexpr int tri_any(int i, int j) { return i >= j ? tri(i, j) : tri(j, i); }
 // parity tolerance. The host simulation runs the SAME formulas; only the hardware seed
 // instructions (v_rsq_f64 / v_rcp_f64, ~2^-23 accurate) are emulated by a float-rounded value.
 #ifdef I2C_HOST_SIM
-I2C_FN double seed_rsq(double x) { return (double)(float)(1.0 / std::sqrt(x)); }
-I2C_FN double seed_rcp(double x) { return (double)(float)(1.0 / x); }
+// (24 significant bits at ANY binary exponent, as the instructions give: a plain cast to float agrees wherever the value is a
+// normal float and overflows / flushes outside, which the instructions do not)
+I2C_FN double seed_round(double v) {
+  int e;
+  const double m = std::frexp(v, &e);  // (0, inf and NaN pass through)
+  return std::ldexp((double)(float)m, e);
+}
+I2C_FN double seed_rsq(double x) { return seed_round(1.0 / std::sqrt(x)); }
+I2C_FN double seed_rcp(double x) { return seed_round(1.0 / x); }
 I2C_FN double m_fma(double a, double b, double c) { return std::fma(a, b, c); }
 I2C_FN double m_rint(double x) { return std::rint(x); }
 I2C_FN double m_fabs(double x) { return std::fabs(x); }
+I2C_FN double m_ldexp(double x, int n) { return std::ldexp(x, n); }
+I2C_FN double m_copysign(double x, double s) { return std::copysign(x, s); }
 I2C_FN float r_rsqrt(float x) { return 1.0f / std::sqrt(x); }
 I2C_FN float r_rcp(float x) { return 1.0f / x; }
 I2C_FN double r_exp(double x) { return std::exp(x); }
@@ -47,6 +56,8 @@ I2C_FN double seed_rcp(double x) { return __builtin_amdgcn_rcp(x); }
 I2C_FN double m_fma(double a, double b, double c) { return fma(a, b, c); }
 I2C_FN double m_rint(double x) { return rint(x); }
 I2C_FN double m_fabs(double x) { return fabs(x); }
+I2C_FN double m_ldexp(double x, int n) { return __builtin_ldexp(x, n); }
+I2C_FN double m_copysign(double x, double s) { return __builtin_copysign(x, s); }
 I2C_FN float r_rsqrt(float x) { return rsqrtf(x); }
 I2C_FN float r_rcp(float x) { return 1.0f / x; }
 I2C_FN float r_exp(float x) { return expf(x); }
@@ -382,6 +393,76 @@ template <typename R> I2C_FN R r_clip(R x, R lo, R hi) { return x < lo ? lo : (x
 I2C_FN double r_clip(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }
 I2C_FN float r_clip(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 #endif
+
+// ---- the wider operation set of model functors: sqrt, tanh and the selects -----------------------------
+// Reached only from functors that call them; the same formulas in the host simulation, the seeds emulated as above.
+//
+// sqrt(x) = x * rsqrt(x) and ONE residual correction s += (x - s^2) * rsqrt(x) / 2 (the product alone carries the rounding of x * y
+// on top of r_rsqrt's; the residual x - s^2 is exact in an FMA). Branch-free: three selects.
+//   * supported: every normal x >= 0 (2.2e-308 .. 1.8e308): <= 1 ulp (measured 0.50 ulp against 50-digit arithmetic on 6 144 arguments,
+//     tests/test_device_math_ops.py holds it to the 2 ulp this file states for its scalar routines);
+//   * +-0 returns the argument (the product would be 0 * inf), +inf returns +inf (inf * 0), x < 0 and NaN give NaN;
+//   * a SUBNORMAL x keeps a finite, non-negative result, but the residual underflows: the relative error grows from 1 ulp at
+//     2.2e-308 to ~2^-27 at 4.9e-324 (the seed of a subnormal has an exponent no double product reaches exactly).
+I2C_FN double r_sqrt(double x) {
+  const double y = r_rsqrt(x);
+  double s = x * y;
+  s = m_fma(m_fma(-s, s, x), 0.5 * y, s);
+  s = x == 0.0 ? x : s;
+  return x == __builtin_inf() ? x : s;
+}
+// tanh(x) = sign(x) D / (2 - D), D = 1 - e^(-2|x|) = -expm1(-2|x|), on the polynomial of r_exp: with -2|x| = n ln 2 + r,
+// expm1(r) = r + r^2 (E'(r^2) + r O'(r^2)) (the two Horner chains of r_exp without their leading 1: no cancellation, relative
+// error ~1 ulp down to the smallest |x|) and D = -(2^n expm1(r) + (2^n - 1)) in one FMA, 2^n - 1 being exact. The expm1 form
+// holds on the whole range, so nothing selects between it and 1 - e^(-2|x|): at n = 0 it IS expm1(r), for n < 0 the constant
+// 2^n - 1 dominates. The quotient is D * rcp(2 - D) with one residual step (2 - D in [1, 2]).
+//   * |x| is clamped to 20: e^-40 < 2^-54, D rounds to 1 and the result is EXACTLY +-1 from |x| >= 20 on (from ~19.1 in fact);
+//     no inf / inf however large |x|; |tanh| <= 1 always; odd to the bit (the sign is copied); NaN in, NaN out;
+//     tanh(+-0) = +-0, a subnormal x returns x.
+//   * measured against 50-digit arithmetic on +-2^-k (k <= 60) and 4 096 points of [-25, 25]: a relative error of 2.73e-16 at
+//     most (glibc's tanh on the same arguments: 2.29e-16).
+I2C_FN double r_tanh(double x) {
+  double a = m_fabs(x);
+  a = a > 20.0 ? 20.0 : a;  // (a NaN stays)
+  const double y = -2.0 * a;
+  const double n = m_rint(y * 1.44269504088896338700e+00);
+  double r = m_fma(-n, 6.93147180369123816490e-01, y);
+  r = m_fma(-n, 1.90821492927058770002e-10, r);
+  const double z = r * r;
+  double e = p_fma(2.08767569878681e-09, z, 2.755731922398589e-07);   // 1/12!, 1/10!
+  double o = p_fma(1.6059043836821613e-10, z, 2.505210838544172e-08);  // 1/13!, 1/11!
+  e = p_fma(e, z, 2.48015873015873e-05);
+  o = p_fma(o, z, 2.7557319223985893e-06);
+  e = p_fma(e, z, 1.388888888888889e-03);
+  o = p_fma(o, z, 1.984126984126984e-04);
+  e = p_fma(e, z, 4.1666666666666664e-02);
+  o = p_fma(o, z, 8.333333333333333e-03);
+  e = p_fma(e, z, 0.5);
+  o = p_fma(o, z, 1.6666666666666666e-01);
+  const double q = m_fma(z, m_fma(r, o, e), r);  // expm1(r)
+  const double t = m_ldexp(1.0, (int)n);
+  const double dd = -m_fma(t, q, t - 1.0);       // 1 - e^(-2|x|), in [0, 1]
+  const double den = 2.0 - dd;
+  const double ry = r_rcp(den);
+  double h = dd * ry;
+  h = m_fma(m_fma(-den, h, dd), ry, h);
+  return m_copysign(h, x);
+}
+#ifdef I2C_HOST_SIM
+I2C_FN float r_sqrt(float x) { return std::sqrt(x); }
+I2C_FN float r_tanh(float x) { return std::tanh(x); }
+I2C_FN float r_abs(float x) { return std::fabs(x); }
+#else
+I2C_FN float r_sqrt(float x) { return sqrtf(x); }
+I2C_FN float r_tanh(float x) { return tanhf(x); }
+I2C_FN float r_abs(float x) { return fabsf(x); }
+#endif
+I2C_FN double r_abs(double x) { return m_fabs(x); }
+// Selects, generic over R. At a tie r_min / r_max return their FIRST argument (which decides whose derivative the dual-number
+// overloads of i2c_linearize.hpp carry); a NaN in the second argument is dropped, one in the first is returned.
+template <typename R> I2C_FN R r_min(R a, R b) { return b < a ? b : a; }
+template <typename R> I2C_FN R r_max(R a, R b) { return b > a ? b : a; }
+template <typename R> I2C_FN R r_where_gt(R a, R b, R x, R y) { return a > b ? x : y; }  // x if a > b else y
 
 // In-place Cholesky of a packed SPD matrix: a <- L (lower), rinv[j] = 1 / L[j][j].
 // Returns false if a pivot is not strictly positive (or NaN): the covariance is not PD.

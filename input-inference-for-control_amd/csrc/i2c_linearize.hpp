@@ -48,7 +48,41 @@ template <typename T> I2C_FN Dual<T> r_exp(const Dual<T>& x) {
   const T e = r_exp(x.v);
   return Dual<T>(e, e * x.d);
 }
-// (the operations a model functor may apply to its arguments: + - * /, r_clip, r_rcp, r_exp, and the sines / cosines it is handed)
+// The wider operation set. Derivative conventions -- the SAME in these overloads and in the analytic Jacobian functor_codegen.py
+// emits (through the helpers next to r_clip_grad below); INTEGRATION.md section 3:
+//   abs' = sign(x), 0 at 0;  max / min: at a tie the FIRST argument's derivative;  where_gt(a, b, x, y): the derivative of the
+//   selected branch, nothing flows through a or b;  sqrt' = rsqrt(x) / 2 (r_sqrt_grad) and rsqrt' = -rsqrt(x)^3 / 2, where a ZERO tangent stays
+//   exactly 0 whatever x is (a select: at x = 0 the product would be inf * 0, and a column the argument does not depend on must
+//   stay zero) and a non-zero one gives +-inf at x = 0;  tanh' = 1 - tanh^2;  log' = rcp(x);  sin' = cos, cos' = -sin.
+template <typename T> I2C_FN T r_tangent(T g, T d) { return d == T(0) ? T(0) : g * d; }  // g d with a zero tangent kept exactly zero
+template <typename T> I2C_FN T r_sqrt_grad(T x) { return x == T(0) ? T(__builtin_inf()) : T(0.5) * r_rsqrt(x); }  // (r_rsqrt(0) is NaN)
+template <typename T> I2C_FN Dual<T> r_sqrt(const Dual<T>& x) { return Dual<T>(r_sqrt(x.v), r_tangent(r_sqrt_grad(x.v), x.d)); }
+template <typename T> I2C_FN Dual<T> r_rsqrt(const Dual<T>& x) {
+  const T r = r_rsqrt(x.v);
+  return Dual<T>(r, r_tangent(T(-0.5) * r * r * r, x.d));
+}
+template <typename T> I2C_FN Dual<T> r_tanh(const Dual<T>& x) {
+  const T t = r_tanh(x.v);
+  return Dual<T>(t, (T(1) - t * t) * x.d);
+}
+template <typename T> I2C_FN Dual<T> r_log(const Dual<T>& x) { return Dual<T>(r_log(x.v), r_rcp(x.v) * x.d); }
+template <typename T> I2C_FN Dual<T> r_abs(const Dual<T>& x) {
+  return Dual<T>(r_abs(x.v), x.v > T(0) ? x.d : (x.v < T(0) ? -x.d : T(0)));
+}
+template <typename T> I2C_FN Dual<T> r_min(const Dual<T>& a, const Dual<T>& b) { return b.v < a.v ? b : a; }
+template <typename T> I2C_FN Dual<T> r_max(const Dual<T>& a, const Dual<T>& b) { return b.v > a.v ? b : a; }
+template <typename T> I2C_FN Dual<T> r_where_gt(const Dual<T>& a, const Dual<T>& b, const Dual<T>& x, const Dual<T>& y) {
+  return a.v > b.v ? x : y;
+}
+// a sine the functor takes itself (of a parameter, a product, an action ...; the angle coordinates are still handed in)
+template <typename T> I2C_FN void r_sincos(const Dual<T>& x, Dual<T>* s, Dual<T>* c) {
+  T sv, cv;
+  r_sincos(x.v, &sv, &cv);
+  *s = Dual<T>(sv, cv * x.d);
+  *c = Dual<T>(cv, -sv * x.d);
+}
+// (the operations a model functor may apply to its arguments: + - * /, r_clip, r_rcp, r_exp, r_sqrt, r_rsqrt, r_tanh, r_log, r_abs,
+// r_min, r_max, r_where_gt, the sines / cosines it is handed and r_sincos of anything else)
 
 enum { FN_DYNAMICS = 0, FN_OBSERVE = 1, FN_OBSERVE_TERMINAL = 2 };
 template <class M, int FN, typename T> I2C_FN void call_model(const T* p, const T* x, const T* sn, const T* cs, T* y) {
@@ -66,6 +100,9 @@ struct has_jacobian<M, FN, R, std::void_t<decltype(M::template jacobian<FN, R>((
                                                                                  (const R*)nullptr, (R*)nullptr, (R*)nullptr))>> : std::true_type {};
 // ... whose derivative of clip is that of r_clip(Dual): 1 strictly inside the limits, 0 on and outside them
 template <typename R> I2C_FN R r_clip_grad(R x, R lo, R hi) { return (x > lo && x < hi) ? R(1) : R(0); }
+// ... of abs: sign(x), 0 at 0 (as r_abs(Dual)); of sqrt / rsqrt: their factor times the tangent through r_tangent above; of min /
+// max / where_gt: r_where_gt on the tangents (for max(a, b): r_where_gt(b, a, db, da), so a tie takes da)
+template <typename R> I2C_FN R r_sign(R x) { return x > R(0) ? R(1) : (x < R(0) ? R(-1) : R(0)); }
 
 // y = f(m) and Jac[k * DIN + j] = d y_k / d m_j for one of the model callbacks (parameters: params_of(), i2c_cell.hpp).
 template <class M, int FN, int DIN, int DOUT, typename R>

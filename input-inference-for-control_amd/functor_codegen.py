@@ -16,6 +16,14 @@ states by hand (csrc/i2c_models.hpp):
     division by a non-constant, integer powers as products;
   * optionally `jacobian<FN, R>()`: value and Jacobian of one function with their common subexpressions shared, which
     value_and_jacobian (csrc/i2c_linearize.hpp) calls instead of d + 1 dual-number passes.
+A model that states `operations = "extended"` (TracedModel.operations; trace(..., operations="extended")) may also use sqrt,
+tanh, log, abs, minimum, maximum, where_gt(a, b, x, y), Python's abs() and half-integer powers, and take the sine of anything: a
+sine whose argument is an integer combination of STATE inputs plus a constant stays an angle coordinate, any other argument (a
+product, a parameter, an action, a nested function) is a GENERAL sine, emitted as one r_sincos call per distinct argument and
+function body, its sine, cosine and derivatives sharing the pair. The derivative conventions of the new nodes are those of the
+dual-number overloads (csrc/i2c_linearize.hpp): abs' = sign (0 at 0), min / max take the first argument's derivative at a tie,
+where_gt the selected branch's, and the tangent of a half-integer power goes through r_tangent (a zero tangent stays zero at 0).
+A basic model traces, refuses and emits exactly as before the wider set existed.
 sympy is imported when the first model is traced, never on import of this module.
 """
 import hashlib
@@ -29,6 +37,9 @@ GEN_DIR = os.path.join(PKG_DIR, "lib", "generated")
 
 FUNCTIONS = ("dynamics", "observe", "observe_terminal", "measure")
 OPERATIONS = "sin, cos, exp, clip(x, lo, hi), rcp, pi and + - * / with integer powers"
+OPERATIONS_EXTENDED = ("sin, cos, exp, sqrt, tanh, log, abs, minimum, maximum, where_gt(a, b, x, y), clip(x, lo, hi), rcp, pi and "
+                       "+ - * / with integer and half-integer powers")
+HINT = ' (a model that sets operations = "extended" may use it)'
 # capacities of the host constants in I2cProblem (checked at registration) and of the one-lane kernels (d <= 8)
 LIMITS = {"d": 8, "NX": 12, "NU": 4, "NZ": 16, "NZT": 16, "NY": 16, "NP": 16}
 INT_KNOBS = ("GROUP", "QUAD_FORWARD_MAX_B", "QUAD_FORWARD_MIN_B", "QUAD_BACKWARD8_MIN_B", "QUAD_BACKWARD8_MAX_B",
@@ -62,6 +73,64 @@ def _make_env():
         def fdiff(self, argindex=1):
             return ClipInside(*self.args) if argindex == 1 else sp.S.Zero
 
+    class WhereGt(sp.Function):
+        """where_gt(a, b, x, y) = x if a > b else y; the derivative of the selected branch, nothing through a or b."""
+        nargs = 4
+
+        def fdiff(self, argindex=1):
+            a, b = self.args[:2]
+            return WhereGt(a, b, sp.S.One, sp.S.Zero) if argindex == 3 else WhereGt(a, b, sp.S.Zero, sp.S.One) if argindex == 4 else sp.S.Zero
+
+    class Max2(sp.Function):
+        """r_max(a, b) = b if b > a else a: at a tie the first argument, and its derivative."""
+        nargs = 2
+
+        def fdiff(self, argindex=1):
+            a, b = self.args
+            return WhereGt(b, a, sp.S.Zero, sp.S.One) if argindex == 1 else WhereGt(b, a, sp.S.One, sp.S.Zero)
+
+    class Min2(sp.Function):
+        """r_min(a, b) = b if b < a else a."""
+        nargs = 2
+
+        def fdiff(self, argindex=1):
+            a, b = self.args
+            return WhereGt(a, b, sp.S.Zero, sp.S.One) if argindex == 1 else WhereGt(a, b, sp.S.One, sp.S.Zero)
+
+    class SignF(sp.Function):
+        """1, -1, and 0 at 0: the derivative of abs (r_sign)."""
+        nargs = 1
+
+        def fdiff(self, argindex=1):
+            return sp.S.Zero
+
+    class AbsF(sp.Function):
+        nargs = 1
+
+        def fdiff(self, argindex=1):
+            return SignF(self.args[0])
+
+    class GSin(sp.Function):
+        """The sine of a general argument: one half of an r_sincos pair (GCos the other)."""
+        nargs = 1
+
+        def fdiff(self, argindex=1):
+            return GCos(self.args[0])
+
+    class GCos(sp.Function):
+        nargs = 1
+
+        def fdiff(self, argindex=1):
+            return -GSin(self.args[0])
+
+    class SqrtGrad(sp.Function):
+        """rsqrt(x) / 2, +inf at 0 (r_sqrt_grad)."""
+        nargs = 1
+
+    class Tangent(sp.Function):
+        """g * d with a zero tangent d kept exactly zero (r_tangent)."""
+        nargs = 2
+
     class SymMath:
         """The operation set of a functor, on sympy expressions."""
         pi = sp.pi
@@ -76,13 +145,35 @@ def _make_env():
             return 1 / sp.sympify(x)
 
         def __getattr__(self, name):
-            raise ValueError(f"m.{name} is outside the operation set of a device functor ({OPERATIONS})")
+            hint = HINT if name in ("sqrt", "tanh", "log", "abs", "minimum", "maximum", "where_gt") else ""
+            raise ValueError(f"m.{name} is outside the operation set of a device functor ({OPERATIONS}){hint}")
 
-    return types.SimpleNamespace(sp=sp, Clip=Clip, ClipInside=ClipInside, math=SymMath())
+    class SymMathExtended(SymMath):
+        """... of a model with operations = "extended"."""
+        sqrt, tanh, log, abs = staticmethod(sp.sqrt), staticmethod(sp.tanh), staticmethod(sp.log), staticmethod(sp.Abs)
+
+        @staticmethod
+        def minimum(a, b):
+            return Min2(sp.sympify(a), sp.sympify(b))
+
+        @staticmethod
+        def maximum(a, b):
+            return Max2(sp.sympify(a), sp.sympify(b))
+
+        @staticmethod
+        def where_gt(a, b, x, y):
+            return WhereGt(*(sp.sympify(v) for v in (a, b, x, y)))
+
+        def __getattr__(self, name):
+            raise ValueError(f"m.{name} is outside the operation set of a device functor ({OPERATIONS_EXTENDED})")
+
+    return types.SimpleNamespace(sp=sp, Clip=Clip, ClipInside=ClipInside, math=SymMath(), math_extended=SymMathExtended(),
+                                 WhereGt=WhereGt, Max2=Max2, Min2=Min2, SignF=SignF, AbsF=AbsF, GSin=GSin, GCos=GCos,
+                                 SqrtGrad=SqrtGrad, Tangent=Tangent)
 
 
-def sym_math():
-    return _env().math
+def sym_math(operations="basic"):
+    return _env().math_extended if operations == "extended" else _env().math
 
 
 class Spec:
@@ -94,6 +185,8 @@ class Spec:
         self.D = self.NX + self.NU
         self.exprs = {}   # function -> [expression per output]
         self.angles = []  # input index of angle a
+        self.extended = False    # operations = "extended"
+        self.general_sines = []  # the distinct arguments of the general sines (extended models), over all functions
 
     def n_in(self, fn):
         return self.D if fn in ("dynamics", "observe") else self.NX
@@ -114,12 +207,16 @@ def check_limits(dims, n_params, who="model"):
         raise ValueError(f"{who}: dim_x, dim_u and dim_z must be at least 1")
 
 
-def trace(dims, fns, n_params, who="model"):
+def trace(dims, fns, n_params, who="model", operations="basic"):
     """dims: {"NX", "NU", "NZ", "NZT", "NY"}; fns: {function name: callable(inputs, p, m)}; -> Spec."""
+    if operations not in ("basic", "extended"):
+        raise ValueError(f"{who}: operations = {operations!r}; a traced model states \"basic\" or \"extended\"")
     check_limits(dims, n_params, who)
     env = _env()
     sp = env.sp
     spec = Spec(dims, n_params)
+    ext = spec.extended = operations == "extended"
+    ops = OPERATIONS_EXTENDED if ext else OPERATIONS
     xs = [sp.Symbol(f"xu{i}", real=True) for i in range(spec.D)]
     ps = [sp.Symbol(f"p{i}", real=True) for i in range(spec.NP)]
     spec.xs, spec.ps = xs, ps
@@ -128,11 +225,11 @@ def trace(dims, fns, n_params, who="model"):
         label = f"{who}.{fn}_fn"
         n_in, n_out = spec.n_in(fn), spec.n_out(fn)
         try:
-            out = fns[fn](list(xs[:n_in]), list(ps), env.math)
+            out = fns[fn](list(xs[:n_in]), list(ps), env.math_extended if ext else env.math)
             out = [] if out is None else list(out)
         except (TypeError, AttributeError) as e:
             raise ValueError(f"{label}: {e} -- a Python branch, comparison or foreign function on a traced value cannot be compiled "
-                             f"(the operation set is {OPERATIONS})") from e
+                             f"(the operation set is {ops})") from e
         except ValueError as e:
             raise ValueError(f"{label}: {e}") from e
         if len(out) != n_out:
@@ -144,8 +241,12 @@ def trace(dims, fns, n_params, who="model"):
     # angles: every sine / cosine brought to sin(xu_j) / cos(xu_j)
     ang = set()
     normal = {}
+    general = set()
     for fn in FUNCTIONS:
-        normal[fn] = [_expand_angles(e, xs[:spec.n_in(fn)], f"{who}.{fn}_fn", k, ang) for k, e in enumerate(raw[fn])]
+        if ext:  # (state inputs only: a sine of anything else is a general sine, not an error)
+            normal[fn] = [_split_sines(_normalise(e), xs[:min(spec.n_in(fn), spec.NX)], ang, general) for e in raw[fn]]
+        else:
+            normal[fn] = [_expand_angles(e, xs[:spec.n_in(fn)], f"{who}.{fn}_fn", k, ang) for k, e in enumerate(raw[fn])]
     spec.angles = sorted(ang)
     if spec.angles and spec.angles[-1] >= spec.NX:
         raise ValueError(f"{who}: the sine / cosine of action input {spec.angles[-1]} occurs; angle coordinates must be states "
@@ -160,8 +261,52 @@ def trace(dims, fns, n_params, who="model"):
     for fn in FUNCTIONS:
         spec.exprs[fn] = [e.xreplace(table) for e in normal[fn]]
         for k, e in enumerate(spec.exprs[fn]):
-            _check_operations(e, allowed, f"{who}.{fn}_fn", k)
+            _check_operations(e, allowed, f"{who}.{fn}_fn", k, ext)
+    spec.general_sines = sorted((a.xreplace(table) for a in general), key=sp.default_sort_key)
     return spec
+
+
+def _normalise(expr):
+    """Extended models: abs() as the node with the derivative convention, and a floating-point exponent that is an integer or a
+    half-integer (x ** 0.5, x ** -1.5, x ** 2.0) as that rational."""
+    env = _env()
+    sp = env.sp
+
+    def exponent(e):
+        return e.is_Pow and e.exp.is_Float and float(2 * e.exp) == int(float(2 * e.exp))
+
+    expr = expr.replace(exponent, lambda e: sp.Pow(e.base, sp.Rational(int(float(2 * e.exp)), 2)))
+    return expr.replace(sp.Abs, env.AbsF)
+
+
+def _split_sines(expr, states, ang, general):
+    """Extended models, bottom-up: a sine / cosine of an integer combination of state inputs plus a constant becomes sines and
+    cosines of single states (angle addition; the states join `ang`), any other one a general sine (its argument joins `general`)."""
+    env = _env()
+    sp = env.sp
+    if expr.is_Atom:
+        return expr
+    args = [_split_sines(a, states, ang, general) for a in expr.args]
+    if any(a is not b for a, b in zip(args, expr.args)):
+        expr = expr.func(*args)
+    if not isinstance(expr, (sp.sin, sp.cos)):
+        return expr
+    arg, new_arg = sp.expand(expr.args[0]), sp.S.Zero
+    for term, coeff in arg.as_coefficients_dict().items():
+        if term == 1 or (term.is_number and not term.free_symbols):
+            new_arg += coeff * term
+        elif term in states and coeff.is_number and float(coeff) == int(float(coeff)):
+            new_arg += sp.Integer(int(float(coeff))) * term
+        else:
+            new_arg = None
+            break
+    if new_arg is not None and not new_arg.atoms(sp.Function):
+        new = sp.expand_trig(expr.func(new_arg))
+        if all(s.args[0] in states for s in new.atoms(sp.sin, sp.cos)):
+            ang.update(states.index(s.args[0]) for s in new.atoms(sp.sin, sp.cos))
+            return new
+    general.add(expr.args[0])
+    return (env.GSin if isinstance(expr, sp.sin) else env.GCos)(expr.args[0])
 
 
 def _expand_angles(expr, inputs, label, k, ang):
@@ -190,9 +335,10 @@ def _expand_angles(expr, inputs, label, k, ang):
     return expr.xreplace(table) if table else expr
 
 
-def _check_operations(e, allowed, label, k):
+def _check_operations(e, allowed, label, k, ext=False):
     env = _env()
     sp = env.sp
+    ops = OPERATIONS_EXTENDED if ext else OPERATIONS
     if e in allowed:
         return
     if not e.free_symbols and e.is_number and not e.atoms(sp.Function):
@@ -201,19 +347,24 @@ def _check_operations(e, allowed, label, k):
         return
     if e.is_Add or e.is_Mul:
         for a in e.args:
-            _check_operations(a, allowed, label, k)
+            _check_operations(a, allowed, label, k, ext)
         return
     if e.is_Pow:
+        half = e.exp.is_Rational and e.exp.q == 2 or e.exp.is_Float and float(2 * e.exp) == int(float(2 * e.exp))
+        if ext and e.exp.is_Rational and e.exp.q == 2:
+            return _check_operations(e.base, allowed, label, k, ext)
         if not e.exp.is_Integer:
             raise ValueError(f"{label}: output {k}: the power {e} has a non-integer exponent, which is outside the operation set "
-                             f"({OPERATIONS})")
-        return _check_operations(e.base, allowed, label, k)
-    if isinstance(e, (sp.exp, env.Clip, env.ClipInside)):
+                             f"({ops})" + (HINT if half and not ext else ""))
+        return _check_operations(e.base, allowed, label, k, ext)
+    if isinstance(e, (sp.exp, env.Clip, env.ClipInside)) or ext and isinstance(
+            e, (sp.tanh, sp.log, env.AbsF, env.SignF, env.Min2, env.Max2, env.WhereGt, env.GSin, env.GCos)):
         for a in e.args:
-            _check_operations(a, allowed, label, k)
+            _check_operations(a, allowed, label, k, ext)
         return
     what = e.func.__name__ if hasattr(e.func, "__name__") else str(e.func)
-    raise ValueError(f"{label}: output {k}: '{what}' in {e} is outside the operation set of a device functor ({OPERATIONS})")
+    raise ValueError(f"{label}: output {k}: '{what}' in {e} is outside the operation set of a device functor ({ops})"
+                     + (HINT if what in ("Abs", "tanh", "log") and not ext else ""))
 
 
 # ---- structure hints and family knobs -------------------------------------------------------------------------------------------
@@ -299,6 +450,12 @@ class _Printer:
             return out
         if e.is_Mul:
             return self.term(e)
+        if e.is_Pow and e.exp.is_Rational and e.exp.q == 2:  # b^(n/2), n odd: b^((n - 1) / 2) r_sqrt(b) or r_rsqrt(b)^|n|
+            n, b = int(e.exp.p), self.expr(e.base)
+            if n < 0:
+                return " * ".join([f"r_rsqrt({b})"] * -n)
+            lead = self.atom(e.base) if not (e.base.is_Mul or e.base.is_Pow) else f"({b})"
+            return " * ".join([lead] * ((n - 1) // 2) + [f"r_sqrt({b})"])
         if e.is_Pow:
             n = int(e.exp)
             b = self.atom(e.base) if not (e.base.is_Mul or e.base.is_Pow) else f"({self.expr(e.base)})"
@@ -310,6 +467,10 @@ class _Printer:
             return "r_clip(" + ", ".join(self.typed(a) for a in e.args) + ")"
         if isinstance(e, env.ClipInside):
             return "r_clip_grad(" + ", ".join(self.typed(a) for a in e.args) + ")"
+        for cls, fn in ((sp.tanh, "r_tanh"), (sp.log, "r_log"), (env.AbsF, "r_abs"), (env.SignF, "r_sign"), (env.Min2, "r_min"),
+                        (env.Max2, "r_max"), (env.WhereGt, "r_where_gt"), (env.SqrtGrad, "r_sqrt_grad"), (env.Tangent, "r_tangent")):
+            if isinstance(e, cls):
+                return f"{fn}(" + ", ".join(self.typed(a) for a in e.args) + ")"
         raise ValueError(f"cannot print {e}")
 
     def typed(self, e):
@@ -344,9 +505,25 @@ class _Printer:
 def _body(names, defs, outs, indent="    "):
     """Straight-line code for `defs` [(symbol, expression)] and `outs` [(target, expression)]: one sympy.cse over all of them, every
     temporary as `const R name = ...;` in dependency order, then `target = expression;` for every output."""
-    sp = _env().sp
+    env = _env()
+    sp = env.sp
     if not outs:
         return ""
+    # general sines (extended models): every distinct argument is one pair (gN, hN) = r_sincos(argument), innermost first
+    pairs, defs, outs = {}, list(defs), list(outs)
+    while True:
+        nodes = set().union(*[e.atoms(env.GSin, env.GCos) for _, e in defs + outs])
+        args = sorted({n.args[0] for n in nodes if not n.args[0].atoms(env.GSin, env.GCos)}, key=sp.default_sort_key)
+        if not args:
+            break
+        table = {}
+        for a in args:
+            g, h = sp.Symbol(f"g{len(pairs)}", real=True), sp.Symbol(f"h{len(pairs)}", real=True)
+            pairs[g] = h
+            defs.append((g, a))  # (the definition of g stands for the pair's call: see below)
+            table[env.GSin(a)], table[env.GCos(a)] = g, h
+        defs = [(s, e if s in table.values() else e.xreplace(table)) for s, e in defs]
+        outs = [(t, e.xreplace(table)) for t, e in outs]
     repl, reduced = sp.cse([e for _, e in defs] + [e for _, e in outs], symbols=sp.numbered_symbols("t"), order="canonical")
     pending = list(repl) + [(s, reduced[i]) for i, (s, _) in enumerate(defs)]
     pr = _Printer(names)
@@ -355,7 +532,12 @@ def _body(names, defs, outs, indent="    "):
     while pending:
         later = []
         for sym, e in pending:
-            if e.free_symbols <= known:
+            if e.free_symbols <= known and sym in pairs:
+                lines.append(f"{indent}R {sym}, {pairs[sym]};\n{indent}r_sincos({pr.typed(e)}, &{sym}, &{pairs[sym]});")
+                for v in (sym, pairs[sym]):
+                    known.add(v)
+                    pr.names[v] = str(v)
+            elif e.free_symbols <= known:
                 lines.append(f"{indent}const R {sym} = {pr.typed(e) if not e.free_symbols else pr.expr(e)};")
                 known.add(sym)
                 pr.names[sym] = str(sym)
@@ -382,7 +564,8 @@ def jacobian_program(spec, fn):
     what it is made of -- the chain rule the dual numbers apply, written out once with the zero terms dropped. (Differentiating
     the whole expression of an output instead swells it, and rounds further from the dual-number path.) The sines are functions
     of their inputs: d sn_a = cs_a, d cs_a = -sn_a where ang(a) = j. -> (defs [(symbol, expression)], values, jacobian row-major)"""
-    sp = _env().sp
+    env = _env()
+    sp = env.sp
     n_in = spec.n_in(fn)
     zero, one = sp.S.Zero, sp.S.One
     grad = {x: [one if i == j else zero for j in range(n_in)] for i, x in enumerate(spec.xs[:n_in])}
@@ -391,7 +574,20 @@ def jacobian_program(spec, fn):
         grad[spec.cs[a]] = [-spec.sn[a] if j == ja else zero for j in range(n_in)]
 
     def derivative(e, j):
-        return sp.Add(*[sp.diff(e, s) * grad[s][j] for s in e.free_symbols if s in grad and grad[s][j] != 0])
+        # (extended models) the outermost half-integer powers are differentiated as symbols of their own, whose tangent goes
+        # through r_tangent: a zero tangent stays exactly zero where the factor rsqrt(base) is infinite
+        halves = sorted((q for q in e.atoms(sp.Pow) if q.exp.is_Rational and q.exp.q == 2), key=sp.default_sort_key) if spec.extended else []
+        halves = [q for q in halves if not any(o is not q and o.base.has(q) for o in halves)]
+        lift, tangent = {}, {}
+        for i, q in enumerate(halves):
+            w, db = sp.Dummy(f"w{i}", real=True), derivative(q.base, j)
+            factor = env.SqrtGrad(q.base) if q.exp == sp.Rational(1, 2) else q.exp * sp.Pow(q.base, q.exp - 1)
+            lift[q], tangent[w] = w, (env.Tangent(factor, db) if db != 0 else zero)
+        if lift:
+            e = e.xreplace(lift)
+        d = sp.Add(*[sp.diff(e, s) * (tangent[s] if s in tangent else grad[s][j]) for s in e.free_symbols
+                     if (tangent[s] if s in tangent else grad[s][j] if s in grad else zero) != 0])
+        return d.xreplace({w: q for q, w in lift.items()}) if lift else d
 
     repl, values = sp.cse(list(spec.exprs[fn]), symbols=sp.numbered_symbols("v"), order="canonical")
     defs = []

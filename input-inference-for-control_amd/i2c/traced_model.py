@@ -17,6 +17,15 @@ observe / observe_terminal / measure, which the oracle takes too), sympy symbols
 structure hints and family knobs, optionally its analytic Jacobian), and nothing else -- there is no second statement of the
 model. resolve_model_id() emits the header under lib/generated/, builds the model library on first use and registers it; the
 model is a plugin (id >= 64), as one brought by a hand-written header is.
+
+A class that sets `operations = "extended"` widens `m` by sqrt, tanh, log, abs, minimum, maximum and where_gt(a, b, x, y) (x where
+a > b, else y), may use Python's abs() and half-integer powers (x ** 0.5, x ** -1.5), and may take the sine of anything: of a
+parameter, a product, an action. Such a functor calls r_sqrt / r_tanh / r_sincos itself, which pins their polynomial constants in
+registers in every kernel it is instantiated in -- hence the statement. The default, "basic", is guaranteed to call no sine and
+no square root. How each operation differentiates (abs' = sign and 0 at 0; min / max: the first argument at a tie; where_gt: the
+selected branch; sqrt: a zero tangent stays zero at 0) is stated in csrc/i2c_linearize.hpp and INTEGRATION.md section 3. Still
+outside: atan2 and the inverse functions, other fractional powers, a Python branch on a traced value. Write a model continuous
+across its kinks: a sigma point within rounding of one must not move a result by more than rounding.
 """
 import importlib.util
 import os
@@ -32,10 +41,17 @@ class NumpyMath:
     """The operation set on NumPy arrays (or floats)."""
     pi = np.pi
     sin, cos, exp, clip = staticmethod(np.sin), staticmethod(np.cos), staticmethod(np.exp), staticmethod(np.clip)
+    # operations = "extended" (sqrt, tanh and log are complex-analytic: the host side still takes complex points through them)
+    sqrt, tanh, log, abs = staticmethod(np.sqrt), staticmethod(np.tanh), staticmethod(np.log), staticmethod(np.abs)
+    minimum, maximum = staticmethod(np.minimum), staticmethod(np.maximum)
 
     @staticmethod
     def rcp(x):
         return 1.0 / x
+
+    @staticmethod
+    def where_gt(a, b, x, y):
+        return np.where(np.asarray(a) > np.asarray(b), x, y)
 
 
 _LOAD_LOCK = threading.Lock()
@@ -64,6 +80,7 @@ class TracedModel(KnownModel):
     jacobian = True    # emit jacobian<FN, R>() for Linearize() (False: dual-number passes, as for a hand-written functor)
     xag_term = None    # terminal target where it is not xag
     struct_name = None  # base name of the device struct and its files (default: the class name)
+    operations = "basic"  # "extended": sqrt, tanh, log, abs, minimum, maximum, where_gt, half-integer powers, sines of anything
 
     def __init__(self, model=None, model_def=None, knobs=None, jacobian=None):
         super().__init__(model, model_def)
@@ -136,14 +153,17 @@ class TracedModel(KnownModel):
         dims["NY"] = self.dim_y
         fns = {"dynamics": self.dynamics_fn, "observe": self.observe_fn, "observe_terminal": self.observe_terminal_fn,
                "measure": self.measure_fn}
-        return cg, cg.trace(dims, fns, n_params, who)
+        if self.operations == "basic":
+            return cg, cg.trace(dims, fns, n_params, who)
+        return cg, cg.trace(dims, fns, n_params, who, operations=self.operations)
 
     def header_text(self):
         """-> (codegen module, struct name, text, file stem); the struct is `<class or struct_name>_<hash of the text>`."""
         cg, spec = self.trace()
         # (the text -- and with it the library's name -- depends on the class's name and functions, not on how its module was imported)
+        origin = f"the Python class {type(self).__name__}" + (f' (operations = "{self.operations}")' if spec.extended else "")
         text, struct, stem = cg.emit_unique(spec, self.struct_name or type(self).__name__, jacobian=self.jacobian, knobs=self.knobs,
-                                            origin=f"the Python class {type(self).__name__}")
+                                            origin=origin)
         return cg, struct, text, stem
 
     def emit(self, out_dir=None):

@@ -37,6 +37,11 @@ def main():
                "-o", os.path.join(d, "x.o"), "-save-temps=obj"]
         subprocess.run(cmd, check=True, capture_output=True, cwd=d)
         lines = open(os.path.join(d, "i2c_model_tu-hip-amdgcn-amd-amdhsa-gfx950.s")).read().split("\n")
+    histogram(lines, pat)
+
+
+def histogram(lines, pat):
+    """Print the histogram of the largest loop of the first kernel of the assembly `lines` whose mangled name matches `pat`."""
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\S*" + pat + r"\S*:", l))
     end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith("s_endpgm"))
     body = lines[start:end]
