@@ -10,8 +10,9 @@
 //
 // Layout: the launch layer of the one-lane kernels (launch(), I2C_KERNEL) and those kernels; the launch layer of the multi-lane
 // kernels (host simulation: sim_teams(); device: I2C_QUAD_SETUP / launch_quad(), the XCD placement) and the group, wave and quad
-// kernels, each with its launcher, and the launcher of the grid kernels; the problem constants, the chunk workspace and the per-model batch sizes; Impl<M, R, S>: which
-// family and schedule serve a call, and the entry points.
+// kernels, each with its launcher, and the launcher of the grid kernels; the problem constants, the chunk workspace and the per-model
+// batch sizes; Impl<M, R, S>: which family and schedule serve a problem (resolve -> Plan), what a call launches beyond that (launches ->
+// Launches: the schedule that runs, the couplings of an i2c_learn iteration's sweeps), the sweeps' launchers and the entry points.
 #pragma once
 #include "i2c_entry.hpp"
 #include "i2c_cell.hpp"
@@ -64,6 +65,7 @@ static int copy_bytes(void* dst, const void* src, size_t n, void*) {
   std::memcpy(dst, src, n);
   return I2C_OK;
 }
+static int sweep_lanes() { return LANE_BLOCK; }  // (the device form's experiment knob does not exist here)
 #else
 #define I2C_KERNEL(BLOCK) __global__ __launch_bounds__(BLOCK) void
 #define I2C_LANE_PARAMS
@@ -333,7 +335,7 @@ I2C_KERNEL(LANE_BLOCK) k_forward_mstep(I2C_LANE_PARAMS const Consts<M, R> c, con
   }
 }
 
-// The forward sweep of i2c_learn with a HELPER wavefront (Impl::forward_helper_on): a workgroup of two waves over the same 64
+// The forward sweep of i2c_learn with a HELPER wavefront (Impl::launches): a workgroup of two waves over the same 64
 // trajectories. Wave 0 is k_forward / k_forward_mstep and releases every chunk of the chunked backward schedule once its messages are
 // stored (ChunkRelease, i2c_cell.hpp); wave 1 -- on another SIMD of the same CU, so it takes no issue slot from the chain -- waits at
 // the workgroup barrier and then composes that chunk with chunk_compose_body, unchanged: the composites are k_chunk_compose's bit
@@ -937,9 +939,9 @@ static void chunk_geometry(int B, int T, int* n_chunks, int* chunk_len) {
   *chunk_len = len;
   *n_chunks = (T + len - 1) / len;
 }
-// Experiment knob (not part of the ABI), read on EVERY backward call: I2C_CHUNK_PASSES=4 runs the chunked schedule as its four passes
-// compose -> stitch -> walk -> reduce wherever the two-launch form (self-stitching walker, deferred reduction) would run: the
-// reference of that form's tests and of its A/B timing.
+// Experiment knob (not part of the ABI), read once on EVERY library call (Impl::launches): I2C_CHUNK_PASSES=4 runs the chunked schedule
+// as its four passes compose -> stitch -> walk -> reduce wherever the two-launch form (self-stitching walker, deferred reduction)
+// would run: the reference of that form's tests and of its A/B timing.
 static bool chunk_four_passes() {
   const char* e = getenv("I2C_CHUNK_PASSES");
   return e && atoi(e) == 4;
@@ -986,7 +988,7 @@ template <class M, typename R, typename S> static ChunkArgs<R, S> chunk_args(con
   template <class M> struct name<M, std::void_t<decltype(M::MEMBER)>> : std::integral_constant<int, M::MEMBER> {};
 // batch size from which I2C_BWD_AUTO runs the fused walk: the model's own measured crossover, or the library-wide default
 I2C_MODEL_CONST(bwd_fused_min_b, BWD_FUSED_MIN_B, I2C_BWD_FUSED_MIN_B)
-// batch size from which the forward sweep of i2c_learn composes the chunks on a helper wave (Impl::forward_helper_on); see
+// batch size from which the forward sweep of i2c_learn composes the chunks on a helper wave (Impl::launches); see
 // ModelDefaults (i2c_models.hpp) for the measurement behind the default
 I2C_MODEL_CONST(forward_helper_min_b, FORWARD_HELPER_MIN_B, 4096)
 // batch window in which the d <= 8 quad backward sweep is the model's DEFAULT; models without the pair: on request only
@@ -1018,7 +1020,7 @@ I2C_MODEL_CONST(quad_chunk_stitch_max_b, QUAD_CHUNK_STITCH_MAX_B, -1)
 // model without them, the grid kernels under I2C_INF_GAUSS_HERMITE; I2C_LANES_QUAD; anything else: I2C_ENOTSUP) as a Request, then
 // walks one ordered rule list per sweep (forward_family, backward_family, propagate_family, filter_family), then the backward schedule
 // and the passes of the chunked one. The two exports report from the plan (family_of, plan); the launchers (run_forward, run_backward,
-// backward_chunked, run_propagate, run_ckf) read the plan and the presence of optional buffers, never the request fields.
+// backward_chunked, run_propagate, run_ckf) read the plan and the call's Launches, never the request fields or a knob.
 
 // What a problem resolves to: families are I2C_FAMILY_* or the negative error code the sweep returns
 struct Plan {
@@ -1029,6 +1031,16 @@ struct Plan {
   int rule;       // the rule variant of the lane bodies: I2C_INF_CUBATURE, _LINEARIZE or _GAUSS_HERMITE
   bool fwd_tm;    // the quad forward sweep writes its messages where a wave / quad backward sweep reads them (Consts::fwd_tm)
   bool fusable;   // i2c_learn_propagate: a forward sweep and the previous propagation may share a launch (k_forward_propagate)
+};
+// What a forward + backward pair of ONE library call launches beyond what the plan says: Impl::launches, at the top of every entry
+// point that runs one, from the plan, the constants, the optional buffers that are present and the knobs. The launchers read it.
+struct Launches {
+  const int schedule;      // the backward schedule that RUNS: the plan's, or its fall-back without a workspace (Impl::schedule_with)
+  const bool self_stitch;  // chunked: the walkers compute their boundary states themselves -- two launches, no stitch pass
+  const bool helper;       // i2c_learn: the lane forward sweep composes the chunks on a helper wave, the chunked schedule starts with its walk
+  const bool defer;        // i2c_learn: the next forward sweep finishes the reduction and the M-step of every iteration but the call's last
+  const bool reduces;      // the backward sweep ends in a reduction kernel (or defers it): the M-step of an iteration rides on that
+  const bool walk_lean;    // the lane walkers, fused and chunked, write no optional output (see chunk_walk_body)
 };
 
 template <class M, typename R, typename S = R> struct Impl {
@@ -1352,13 +1364,59 @@ template <class M, typename R, typename S = R> struct Impl {
     return make_consts<M, R>(&q, 0.0, 0);
   }
 
-  // ---- the sweeps: each written once for either storage type, dispatched from the plan --------------------------------------------
-  // `pend` (i2c_learn only, see defers_mstep): the previous iteration's reduction and M-step, finished in this sweep's prologue
-  // `helper` (i2c_learn only, see forward_helper_on): the chunks of the backward sweep that follows, composed beside this sweep
-  static int run_forward(const I2cProblem* p, const Plan& pl, const C& c, const void* prior, void* fwd, void* prior_out, int32_t* status,
-                         void* stream, const PendingMstep<R>* pend = nullptr, const ChunkArgs<R, S>* helper = nullptr) {
+  // ---- what a call launches beyond its plan ---------------------------------------------------------------------------------------
+  // The two-launch form of the chunked schedule (compose, self-stitching walk) and the forward sweep's helper wave exist for the d <= 5
+  // lane models ...
+  static constexpr bool SELF_STITCH = LANE && C::D <= 5;
+  // ... and run where the chunked schedule runs under the sigma-point rule, for problems without a terminal state prior (whose end of
+  // the chain advances temp[b]: once per trajectory, so not by several walkers). The walkers stitch themselves where the stitch and
+  // walk passes are the lane kernels'. `in_learn` (i2c_learn alone: every forward sweep is followed by this plan's backward sweep): the
+  // lane forward sweep composes the chunks on a second wave (k_forward_helper) where the compose pass is the lane kernels', 64 lanes to
+  // a wave, from the batch size at which it pays (forward_helper_min_b: short chunks leave the helper no more time to compose a chunk
+  // than the sweep takes to produce the next), and its M-step prologue (k_forward_mstep) takes the reduction behind such walkers.
+  // Knobs (not part of the ABI), read HERE, once per library call -- the tests flip them inside one process: I2C_CHUNK_PASSES=4
+  // (chunk_four_passes) brings back the four passes and the sweep without the helper; I2C_FORWARD_HELPER=0 that sweep and the compose
+  // launch (the reference of tests/test_forward_helper.py and of the A/B timing), any other value the helper below forward_helper_min_b.
+  static Launches launches(const I2cProblem* p, const Plan& pl, const C& c, const void* xm, const void* zpost, const void* cell_stats,
+                           const bool in_learn) {
+    const int mode = schedule_with(pl, p->work != nullptr);
+    const bool chunked = mode == I2C_BWD_CHUNKED;  // (the plan answers it for the lane family and the d <= 8 quad walker: backward_chunked)
+    const bool two_launch = SELF_STITCH && chunked && pl.rule == I2C_INF_CUBATURE && !c.has_x_terminal && !chunk_four_passes();
+    const bool self = two_launch && pl.stitch == I2C_FAMILY_LANE && pl.walker == I2C_FAMILY_LANE;
+    const bool lane_forward = in_learn && two_launch && pl.forward == I2C_FAMILY_LANE;
+    bool helper = lane_forward && pl.compose == I2C_FAMILY_LANE && LANE_BLOCK == 64 && sweep_lanes() == LANE_BLOCK;
+    if (helper) {
+      const char* e = getenv("I2C_FORWARD_HELPER");
+      helper = e ? strcmp(e, "0") != 0 : p->B >= forward_helper_min_b<M>::value;
+    }
+    // a reduction: the chunked and the two-pass schedule's (lane: neither chunked nor fused; wave: given its workspaces), no walk's
+    const bool reduces = pl.backward == I2C_FAMILY_WAVE   ? mode == I2C_BWD_TWO_PASS && xm && cell_stats
+                         : pl.backward == I2C_FAMILY_LANE ? mode != I2C_BWD_FUSED
+                                                          : chunked;
+    return Launches{mode, self, helper, lane_forward && self, reduces, I2C_WALK_LEAN && !xm && !zpost && !cell_stats && !c.z_per_cell};
+  }
+
+  // ---- the sweeps: each written once for either storage type, dispatched from the plan and the call's Launches ---------------------
+  // The lane forward sweep under the sigma-point rule: k_forward, with the prologue of a pending M-step, with the helper wave (two
+  // waves per workgroup: the sweep, and the compose pass of the backward sweep behind it) or with both
+  template <bool LEAN>
+  static int launch_forward_lane(const I2cProblem* p, const Launches& L, const C& c, const FwdArgs<R, S>& a, const PendingMstep<R>& pend, void* stream) {
+    const int lanes = sweep_lanes();
+    if constexpr (SELF_STITCH) {
+      if (L.helper) {
+        constexpr int W = HELPER_WAVES;
+        const ChunkArgs<R, S> ch = chunk_args<M>(p, CellArgs<R, S>{a.fwd});  // (the compose pass reads the forward messages only)
+        return pend.part ? launch(k_forward_mstep_helper<M, R, LEAN, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, ch, pend)
+                         : launch(k_forward_helper<M, R, LEAN, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, ch);
+      }
+      if (pend.part) return launch(k_forward_mstep<M, R, LEAN, S>, p->B, 1, lanes, stream, c, a, lanes, pend);
+    }
+    return launch(k_forward<M, R, LEAN, false, S>, p->B, 1, lanes, stream, c, a, lanes);
+  }
+  // `pend` (i2c_learn only, Launches::defer; .part set): the previous iteration's reduction and M-step, finished in this sweep's prologue
+  static int run_forward(const I2cProblem* p, const Plan& pl, const Launches& L, const C& c, const void* prior, void* fwd, void* prior_out,
+                         int32_t* status, void* stream, const PendingMstep<R>& pend = {}) {
     if (pl.forward < 0) return pl.forward;
-    if (pend && !defers_mstep(pl)) return I2C_EINVAL;  // (only the lane sweep below has the prologue)
     const FwdArgs<R, S> a{(const S*)prior, (S*)fwd, (S*)prior_out, (const R*)p->x0, (const R*)p->sig_x0,
                           (const R*)p->z,  (const R*)p->alpha, (const R*)p->alpha_cell, p->feedforward, status, p->expert};
     if (pl.forward == I2C_FAMILY_WAVE) {
@@ -1382,95 +1440,37 @@ template <class M, typename R, typename S = R> struct Impl {
         if (pl.rule == I2C_INF_LINEARIZE) return launch(k_forward_lin<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
         if (pl.rule == I2C_INF_GAUSS_HERMITE) return launch(k_forward<M, R, false, true>, p->B, 1, LANE_BLOCK, stream, c, a, LANE_BLOCK);
       }
-#ifdef I2C_HOST_SIM
-      const int lanes = LANE_BLOCK;
-#else
-      const int lanes = sweep_lanes();
-#endif
       const bool lean = c.rule_xu.unit && c.rule_x.unit && !c.z_per_cell && !a.alpha_cell && !a.prior_out && c.t0 == 0;
-      if (plan_trace()) fprintf(stderr, "i2c_forward_lane: sweep=%s\n", SELF_STITCH && helper ? "helper" : "plain");
-      if constexpr (SELF_STITCH) {
-        if (helper) {  // (forward_helper_on) two waves per workgroup: the sweep, and the compose pass of the backward sweep behind it
-          constexpr int W = HELPER_WAVES;
-          if (pend) return lean ? launch(k_forward_mstep_helper<M, R, true, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, *helper, *pend)
-                                : launch(k_forward_mstep_helper<M, R, false, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, *helper, *pend);
-          return lean ? launch(k_forward_helper<M, R, true, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, *helper)
-                      : launch(k_forward_helper<M, R, false, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, *helper);
-        }
-      }
-      if constexpr (SELF_STITCH) {
-        if (pend) return lean ? launch(k_forward_mstep<M, R, true, S>, p->B, 1, lanes, stream, c, a, lanes, *pend)
-                              : launch(k_forward_mstep<M, R, false, S>, p->B, 1, lanes, stream, c, a, lanes, *pend);
-      }
-      if (lean) return launch(k_forward<M, R, true, false, S>, p->B, 1, lanes, stream, c, a, lanes);
-      return launch(k_forward<M, R, false, false, S>, p->B, 1, lanes, stream, c, a, lanes);
+      if (plan_trace()) fprintf(stderr, "i2c_forward_lane: sweep=%s\n", L.helper ? "helper" : "plain");
+      return lean ? launch_forward_lane<true>(p, L, c, a, pend, stream) : launch_forward_lane<false>(p, L, c, a, pend, stream);
     }
     return I2C_ENOTSUP;
   }
   static int forward(const I2cProblem* p, const void* prior, void* fwd, void* prior_out, int32_t* status, void* stream) {
-    return run_forward(p, resolve(p), forward_consts(p), prior, fwd, prior_out, status, stream);
+    const Plan pl = resolve(p);
+    const C c = forward_consts(p);
+    return run_forward(p, pl, launches(p, pl, c, nullptr, nullptr, nullptr, false), c, prior, fwd, prior_out, status, stream);
   }
 
-  // `fuse` (i2c_learn only): run the M-step inside the reduction kernel of the two-pass / chunked schedules.
-  struct MstepFuse {
-    double tol;
-    int update;
-    void* stats_out;
-    bool done;
-    bool defer;               // in: the caller's next forward sweep can finish the reduction and the M-step (defers_mstep)
-    bool deferred;            // out: it has to -- the schedule did not launch its reduction --,
-    PendingMstep<R> pending;  //      with these arguments
-    bool composed;            // in: the caller's forward sweep has composed the chunks (forward_helper_on): the schedule starts behind its compose pass
-  };
-  // Experiment knob (not part of the ABI), read on EVERY i2c_learn call: I2C_FORWARD_HELPER=0 brings back the forward sweep without
-  // the helper wave and the compose launch of the backward sweep -- the reference of tests/test_forward_helper.py and of the A/B
-  // timing --, as does I2C_CHUNK_PASSES=4 (the reference of tests/test_chunk_self_stitch.py stays as it was); any other value runs the
-  // helper at every batch size its window allows, below the model's forward_helper_min_b too. -1: not set.
-  static int forward_helper_knob() {
-    const char* e = getenv("I2C_FORWARD_HELPER");
-    if (chunk_four_passes() || (e && strcmp(e, "0") == 0)) return 0;
-    return e ? 1 : -1;
-  }
-  // i2c_learn: the forward sweep composes the chunks of the backward sweep behind it on a second wave (k_forward_helper) where that
-  // sweep is known to be this plan's chunked schedule with a lane compose pass over an existing workspace, and the forward sweep the
-  // lane kernel of a d <= 5 model under the sigma-point rule, 64 lanes to a wave, from the batch size at which it pays
-  // (forward_helper_min_b: short chunks leave the helper no more time to compose a chunk than the sweep takes to produce the next).
-  // A terminal state prior keeps the four passes.
-  static bool forward_helper_on(const I2cProblem* p, const Plan& pl, const C& c) {
-#ifndef I2C_HOST_SIM
-    if (sweep_lanes() != LANE_BLOCK) return false;
-#endif
-    const int knob = forward_helper_knob();
-    if (knob == 0 || (knob < 0 && p->B < forward_helper_min_b<M>::value)) return false;
-    const bool to_chunked = pl.backward == I2C_FAMILY_LANE || (QUAD8 && pl.backward == I2C_FAMILY_QUAD);  // run_backward's own test
-    return SELF_STITCH && LANE_BLOCK == 64 && pl.forward == I2C_FAMILY_LANE && pl.rule == I2C_INF_CUBATURE && to_chunked &&
-           schedule_with(pl, p->work != nullptr) == I2C_BWD_CHUNKED && pl.compose == I2C_FAMILY_LANE && !c.has_x_terminal;
-  }
-  // The two-launch form of the chunked schedule (compose, self-stitching walk) exists for the d <= 5 lane models ...
-  static constexpr bool SELF_STITCH = LANE && C::D <= 5;
-  // ... and runs under the sigma-point rule with lane stitch and walk passes, for problems without a terminal state prior (whose end
-  // of the chain advances temp[b]: once per trajectory, so not by several walkers)
-  static bool self_stitches(const Plan& pl, const C& c) {
-    return SELF_STITCH && pl.rule == I2C_INF_CUBATURE && pl.stitch == I2C_FAMILY_LANE && pl.walker == I2C_FAMILY_LANE && !c.has_x_terminal &&
-           !chunk_four_passes();
-  }
-  // i2c_learn: the forward sweep of the next iteration is the lane k_forward, which has the variant with the M-step prologue
-  static bool defers_mstep(const Plan& pl) { return SELF_STITCH && pl.rule == I2C_INF_CUBATURE && pl.forward == I2C_FAMILY_LANE; }
   // Linearize() applies the terminal cost at the END of the chain, with the temperature of the cell that sits there
   // (i2c.py:475-491: the cell's own sig_xi_terminal). A receding-horizon loop appends cells that keep the temperature they were
   // copied with (I2cProblem.alpha_cell), so after the first shift that is not the graph's alpha.
   static const R* terminal_alpha(const I2cProblem* p, const C& c) {
     return p->alpha_cell ? (const R*)p->alpha_cell + (long)c.row(p->T - 1) * (long)p->B : (const R*)p->alpha;
   }
-  // `c`: the constants of the call with the M-step's tolerance where `fuse` is set
-  static int run_backward(const I2cProblem* p, const Plan& pl, const C& c, const void* fwd, void* xm, void* post, void* zpost, void* cell_stats,
-                          void* term_stats, int32_t* status, void* stream, MstepFuse* fuse) {
+  // the M-step an iteration of i2c_learn ends with (run_mstep, or riding on a reduction: Launches::reduces), and a stand-alone sweep's none
+  static MstepArgs<R> mstep_args(const I2cProblem* p, const void* term_stats, void* stats_out, const int update = 1) {
+    return MstepArgs<R>{(const R*)term_stats, (R*)p->alpha, (R*)stats_out, update};
+  }
+  static MstepArgs<R> no_mstep(const void* term_stats) { return MstepArgs<R>{(const R*)term_stats, nullptr, nullptr, 0}; }
+  // `c`: the constants of the call, with the M-step's tolerance where `ms` is one; `last`: the call's last iteration (Launches::defer)
+  static int run_backward(const I2cProblem* p, const Plan& pl, const Launches& L, const C& c, const void* fwd, void* xm, void* post, void* zpost,
+                          void* cell_stats, void* term_stats, int32_t* status, void* stream, const MstepArgs<R>& ms, const bool last = true) {
     if (pl.backward < 0) return pl.backward;
     if (pl.schedule < 0) return pl.schedule;
-    const MstepArgs<R> ms{(const R*)term_stats, fuse ? (R*)p->alpha : nullptr, fuse ? (R*)fuse->stats_out : nullptr, fuse ? fuse->update : 0};
     const CellArgs<R, S> a{(const S*)fwd,  (const S*)xm,   (const R*)p->z, (S*)post, (S*)zpost,
                            (R*)cell_stats, (R*)term_stats, (R*)p->temp,    status,   terminal_alpha(p, c)};
-    const int mode = schedule_with(pl, p->work != nullptr);
+    const int mode = L.schedule;
     int rc = I2C_ENOTSUP;
     if (pl.backward == I2C_FAMILY_WAVE) {
       // the fused walk; two-pass (scan, one wave per cell, reduction -- with the M-step riding on it in i2c_learn) when that schedule
@@ -1480,14 +1480,13 @@ template <class M, typename R, typename S = R> struct Impl {
         rc = launch_wave<WK_SCAN, M, R, S>(c, a, stream);
         if (rc == I2C_OK) rc = launch_wave<WK_CELL, M, R, S>(c, a, stream);
         if (rc == I2C_OK) rc = launch_reduce<M, R>(c, a, ms, p->T, stream);
-        if (fuse) fuse->done = true;
       }
       return rc;
     }
     if (pl.backward == I2C_FAMILY_QUAD) {
       if constexpr (HAS_QUAD_BACKWARD) {
         if constexpr (QUAD8) {
-          if (mode == I2C_BWD_CHUNKED) return backward_chunked(p, pl, c, a, ms, fuse, stream);
+          if (mode == I2C_BWD_CHUNKED) return backward_chunked(p, pl, L, c, a, ms, last, stream);
         }
         return launch_quad_backward<M, R, S>(c, a, stream);
       }
@@ -1499,44 +1498,42 @@ template <class M, typename R, typename S = R> struct Impl {
       if constexpr (HAS_GRID) return launch_grid<GRK_BACKWARD, M, R>(c, a, stream);
     }
     if constexpr (LANE) {
-      if (mode == I2C_BWD_CHUNKED) return backward_chunked(p, pl, c, a, ms, fuse, stream);
+      if (mode == I2C_BWD_CHUNKED) return backward_chunked(p, pl, L, c, a, ms, last, stream);
       if (mode == I2C_BWD_FUSED) {  // a lane per trajectory walks T-1..0
         if constexpr (!MIXED) {
           if (pl.rule == I2C_INF_LINEARIZE) return launch(k_bwd_lin<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
           if (pl.rule == I2C_INF_GAUSS_HERMITE) return launch(k_bwd_fused<M, R, true>, p->B, 1, LANE_BLOCK, stream, c, a);
         }
-        const bool lean = I2C_WALK_LEAN && !a.xm && !a.zpost && !a.cell_stats && !c.z_per_cell;  // see chunk_walk_body
-        return lean ? launch(k_bwd_fused<M, R, false, S, true>, p->B, 1, LANE_BLOCK, stream, c, a)
-                    : launch(k_bwd_fused<M, R, false, S>, p->B, 1, LANE_BLOCK, stream, c, a);
+        return L.walk_lean ? launch(k_bwd_fused<M, R, false, S, true>, p->B, 1, LANE_BLOCK, stream, c, a)
+                           : launch(k_bwd_fused<M, R, false, S>, p->B, 1, LANE_BLOCK, stream, c, a);
       }
       if (!a.xm || !a.cell_stats) return I2C_EINVAL;  // two-pass needs both as workspace
       const ScanArgs<R, S> sc{a.fwd, const_cast<S*>(a.xm), (R*)p->temp, a.status};
       rc = launch(k_scan<M, R, S>, p->B, 1, LANE_BLOCK, stream, c, sc);
       if (rc == I2C_OK) rc = launch(k_cell<M, R, S>, p->B, p->T, CELL_BLOCK, stream, c, a);
       if (rc == I2C_OK) rc = launch_reduce<M, R>(c, a, ms, p->T, stream);
-      if (fuse) fuse->done = true;
     }
     return rc;
   }
   // The chunked schedule for every rule: compose (one lane per trajectory and chunk) -> stitch -> walk -> reduce; in the two-launch form
-  // (self_stitches) compose -> self-stitching walk, then the reduction, unless i2c_learn's next forward sweep takes it. Sigma-point rule: each
-  // of the first three passes on the lane kernels or in the quad form (four trajectories per wavefront), as the plan says. Linearize
-  // and Gauss-Hermite (fp64 storage): the lane kernels, with their own stitch and walk -- the composition of the x-marginal recursion
-  // has no transform in it --, and Linearize its own reduction over the chunks' partial sums.
-  static int backward_chunked(const I2cProblem* p, const Plan& pl, const C& c, const CellArgs<R, S>& a, const MstepArgs<R>& ms, MstepFuse* fuse,
-                              void* stream) {
+  // (Launches::self_stitch) compose -> self-stitching walk, then the reduction, unless i2c_learn's next forward sweep takes it
+  // (Launches::defer, every iteration but the `last`); behind a forward sweep with the helper wave (Launches::helper) the composites
+  // are written and the schedule starts behind its compose pass. Sigma-point rule: each of the first three passes on the lane kernels
+  // or in the quad form (four trajectories per wavefront), as the plan says. Linearize and Gauss-Hermite (fp64 storage): the lane
+  // kernels, with their own stitch and walk -- the composition of the x-marginal recursion has no transform in it --, and Linearize
+  // its own reduction over the chunks' partial sums.
+  static int backward_chunked(const I2cProblem* p, const Plan& pl, const Launches& L, const C& c, const CellArgs<R, S>& a, const MstepArgs<R>& ms,
+                              const bool last, void* stream) {
     int rc = I2C_ENOTSUP;
     if constexpr (LANE) {
       const ChunkArgs<R, S> ch = chunk_args<M>(p, a);
       const long B = p->B;
       const int nc = ch.n_chunks;
       const bool lin = !MIXED && pl.rule == I2C_INF_LINEARIZE, gh = !MIXED && pl.rule == I2C_INF_GAUSS_HERMITE;
-      const bool self = self_stitches(pl, c);
-      if (fuse) fuse->done = true;  // the M-step rides on this schedule's reduction (set whether or not a pass fails to launch)
+      const bool self = L.self_stitch;
       // compose
-      const bool composed = fuse && fuse->composed;  // (the helper wave of the caller's forward sweep has written the composites)
-      if (plan_trace()) fprintf(stderr, "i2c_backward_chunked: compose=%s\n", composed ? "skipped" : "launched");
-      if (composed) {
+      if (plan_trace()) fprintf(stderr, "i2c_backward_chunked: compose=%s\n", L.helper ? "skipped" : "launched");
+      if (L.helper) {
         rc = I2C_OK;
       } else if (pl.compose == I2C_FAMILY_QUAD) {
         if constexpr (QUAD8) rc = launch_quad_chunk_compose<M, R, S>(c, ch, stream);
@@ -1565,7 +1562,7 @@ template <class M, typename R, typename S = R> struct Impl {
         if constexpr (!MIXED)
           rc = lin ? launch(k_chunk_walk_lin<M, R>, B, nc, LANE_BLOCK, stream, c, ch) : launch(k_chunk_walk<M, R, R, false, true>, B, nc, LANE_BLOCK, stream, c, ch);
       } else {
-        const bool lean = I2C_WALK_LEAN && !a.xm && !a.zpost && !a.cell_stats && !c.z_per_cell;  // see chunk_walk_body
+        const bool lean = L.walk_lean;
         if constexpr (SELF_STITCH) {
           if (self)
             rc = lean ? launch(k_chunk_walk_self<M, R, S, true>, B, nc, LANE_BLOCK, stream, c, ch)
@@ -1577,10 +1574,7 @@ template <class M, typename R, typename S = R> struct Impl {
       // reduce
       if (lin) {
         if constexpr (!MIXED) rc = launch(k_chunk_reduce_lin<M, R>, B, 1, LANE_BLOCK, stream, c, ch, ms);
-      } else if (self && fuse && fuse->defer) {  // finish_pending_mstep, in the prologue of the caller's next forward sweep
-        fuse->deferred = true;
-        fuse->pending = PendingMstep<R>{ch.part, a.term_stats, ms, nc, c.tol};
-      } else {
+      } else if (!L.defer || last) {  // (deferred: finish_pending_mstep in the prologue of the caller's next forward sweep, pending_mstep)
         C cr = c;  // reduction over chunks instead of cells: same kernel, T := number of chunks
         cr.T = nc;
         CellArgs<R, S> ared = a;
@@ -1592,7 +1586,10 @@ template <class M, typename R, typename S = R> struct Impl {
   }
   static int backward(const I2cProblem* p, const void* fwd, void* xm, void* post, void* zpost, void* cell_stats,
                       void* term_stats, int32_t* status, void* stream) {
-    return run_backward(p, resolve(p), make_consts<M, R>(p, 0.0, 0), fwd, xm, post, zpost, cell_stats, term_stats, status, stream, nullptr);
+    const Plan pl = resolve(p);
+    const C c = make_consts<M, R>(p, 0.0, 0);
+    return run_backward(p, pl, launches(p, pl, c, xm, zpost, cell_stats, false), c, fwd, xm, post, zpost, cell_stats, term_stats, status, stream,
+                        no_mstep(term_stats));
   }
 
   static int riccati(const I2cProblem* p, const void* prior_out, const void* fwd, const void* xm, void* post, void* ric,
@@ -1609,12 +1606,11 @@ template <class M, typename R, typename S = R> struct Impl {
   }
 
   // `c`: the constants of the call with the M-step's tolerance
-  static int run_mstep(const I2cProblem* p, const C& c, const void* term_stats, int update, void* stats_out, void* stream) {
-    MstepArgs<R> a{(const R*)term_stats, (R*)p->alpha, (R*)stats_out, update};
+  static int run_mstep(const I2cProblem* p, const C& c, const MstepArgs<R>& a, void* stream) {
     return launch(k_mstep<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
   }
   static int mstep(const I2cProblem* p, const void* term_stats, double tol, int update, void* stats_out, void* stream) {
-    return run_mstep(p, make_consts<M, R>(p, tol, 0), term_stats, update, stats_out, stream);
+    return run_mstep(p, make_consts<M, R>(p, tol, 0), mstep_args(p, term_stats, stats_out, update), stream);
   }
 
   // _update_priors (i2c.py:1210-1213): cells with index <= tau switch to feedback mode
@@ -1628,28 +1624,31 @@ template <class M, typename R, typename S = R> struct Impl {
                    void* stream) {
     const Plan pl = resolve(p);
     const C cf = forward_consts(p), cb = make_consts<M, R>(p, tol, 0);
+    const Launches L = launches(p, pl, cb, xm, zpost, cell_stats, true);
     // Behind a self-stitching chunked backward sweep the reduction and the M-step of iteration `it` run in the prologue of iteration
     // it + 1's forward sweep (k_forward_mstep); the last iteration of the call ends with k_reduce as a backward sweep on its own does.
-    PendingMstep<R> pend{};
-    bool have_pend = false;
-    // Every forward sweep of the call is followed by this plan's backward sweep: where that is the chunked schedule, the sweep's
-    // helper wave composes its chunks (forward_helper_on) and the schedule starts with its walk.
-    const bool helper = forward_helper_on(p, pl, cf);
-    CellArgs<R, S> of_fwd{};  // (the compose pass reads the forward messages only)
-    of_fwd.fwd = (const S*)fwd;
-    const ChunkArgs<R, S> chunks = helper ? chunk_args<M>(p, of_fwd) : ChunkArgs<R, S>{};
+    PendingMstep<R> pend{};  // (.part == nullptr: none)
     for (int it = 0; it < n_iters; ++it) {
-      void* stats = (R*)stats_hist + (size_t)it * 4 * p->B;
-      MstepFuse fuse{tol, 1, stats, false, it + 1 < n_iters && defers_mstep(pl), false, {}, helper};
-      int rc = run_forward(p, pl, cf, post, fwd, nullptr, status, stream, have_pend ? &pend : nullptr, helper ? &chunks : nullptr);
-      have_pend = false;
-      if (rc == I2C_OK) rc = run_backward(p, pl, cb, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, &fuse);
-      if (rc == I2C_OK && fuse.deferred) pend = fuse.pending, have_pend = true;
-      if (rc == I2C_OK && !fuse.done) rc = run_mstep(p, cb, term_stats, 1, stats, stream);  // fused / group / Linearize / Gauss-Hermite walks have no reduction kernel
-      if (rc == I2C_OK && tau > 0 && it == 0) rc = to_feedback(p, tau, stream);  // idempotent: once per call
+      const bool last = it + 1 == n_iters;
+      const MstepArgs<R> ms = mstep_args(p, term_stats, (R*)stats_hist + (size_t)it * 4 * p->B);
+      int rc = run_forward(p, pl, L, cf, post, fwd, nullptr, status, stream, pend);
+      if (rc == I2C_OK) rc = run_backward(p, pl, L, cb, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, ms, last);
+      pend = (L.defer && !last) ? pending_mstep(p, cb, term_stats, ms) : PendingMstep<R>{};
+      if (rc == I2C_OK) rc = finish_iteration(p, L, cb, ms, tau, it, stream);
       if (rc != I2C_OK) return rc;
     }
     return I2C_OK;
+  }
+  // what the forward sweep behind a deferring backward sweep finishes: the walkers' partial sums in the chunk workspace, and this M-step
+  static PendingMstep<R> pending_mstep(const I2cProblem* p, const C& c, void* term_stats, const MstepArgs<R>& ms) {
+    const ChunkArgs<R, S> ch = chunk_args<M>(p, CellArgs<R, S>{});
+    return PendingMstep<R>{ch.part, (R*)term_stats, ms, ch.n_chunks, c.tol};
+  }
+  // the tail of an EM iteration: the M-step in a kernel of its own where no reduction carried it, and after the first one the mode flags
+  static int finish_iteration(const I2cProblem* p, const Launches& L, const C& c, const MstepArgs<R>& ms, const int tau, const int it, void* stream) {
+    int rc = L.reduces ? I2C_OK : run_mstep(p, c, ms, stream);  // fused / group / Linearize / Gauss-Hermite walks have no reduction kernel
+    if (rc == I2C_OK && tau > 0 && it == 0) rc = to_feedback(p, tau, stream);  // idempotent: once per call
+    return rc;
   }
 
   // n_iters EM iterations WITH closed-loop propagation (covariance control: learn_msgs with _propagate, i2c.py:1238-1251) enqueued by
@@ -1663,6 +1662,7 @@ template <class M, typename R, typename S = R> struct Impl {
     if constexpr (MIXED) return I2C_ENOTSUP;
     const Plan pl = resolve(p);
     const C cf = forward_consts(p), cb = make_consts<M, R>(p, tol, 0), cp = propagate_consts(p, use_expert);
+    const Launches L = launches(p, pl, cb, xm, zpost, cell_stats, false);
     auto prop_row = [&](int it) { return (void*)((R*)prop_hist + (size_t)it * 3 * p->B); };
     int pending = -1;  // iteration whose propagation has not run yet
     for (int it = 0; it < n_iters; ++it) {
@@ -1685,12 +1685,11 @@ template <class M, typename R, typename S = R> struct Impl {
           pending = -1;
           if (rc != I2C_OK) return rc;
         }
-        rc = run_forward(p, pl, cf, post, fwd, nullptr, status, stream);
+        rc = run_forward(p, pl, L, cf, post, fwd, nullptr, status, stream);
       }
       if (rc != I2C_OK) return rc;
-      void* stats = (R*)stats_hist + (size_t)it * 4 * p->B;
-      MstepFuse fuse{tol, 1, stats, false};
-      rc = run_backward(p, pl, cb, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, &fuse);
+      const MstepArgs<R> ms = mstep_args(p, term_stats, (R*)stats_hist + (size_t)it * 4 * p->B);
+      rc = run_backward(p, pl, L, cb, fwd, xm, post, zpost, cell_stats, term_stats, status, stream, ms);
       if (rc != I2C_OK) return rc;
       if (it == 0) {  // in order: the mode flags change right after this M-step
         rc = run_propagate(p, pl, cp, post, prop, prop_row(0), status, stream);
@@ -1698,8 +1697,7 @@ template <class M, typename R, typename S = R> struct Impl {
       } else {
         pending = it;
       }
-      if (!fuse.done) rc = run_mstep(p, cb, term_stats, 1, stats, stream);
-      if (rc == I2C_OK && tau > 0 && it == 0) rc = to_feedback(p, tau, stream);
+      rc = finish_iteration(p, L, cb, ms, tau, it, stream);
       if (rc != I2C_OK) return rc;
     }
     if (pending >= 0) return run_propagate(p, pl, cp, post, prop, prop_row(pending), status, stream);
@@ -1735,11 +1733,12 @@ template <class M, typename R, typename S = R> struct Impl {
     if constexpr (MIXED) return I2C_ENOTSUP;
     const Plan pl = resolve(p);
     const C cf = forward_consts(p), cb = make_consts<M, R>(p, 0.0, 0);
+    const Launches L = launches(p, pl, cb, m->xm, m->zpost, m->cell_stats, false);
     int rc = I2C_OK;
     if (m->do_filter) rc = run_ckf(p, pl, m->sig_zeta, m->y, m->u, const_cast<void*>(p->x0), const_cast<void*>(p->sig_x0), m->status, stream);
     for (int it = 0; it < m->n_iter && rc == I2C_OK; ++it) {
-      rc = run_forward(p, pl, cf, m->post, m->fwd, nullptr, m->status, stream);
-      if (rc == I2C_OK) rc = run_backward(p, pl, cb, m->fwd, m->xm, m->post, m->zpost, m->cell_stats, m->term_stats, m->status, stream, nullptr);
+      rc = run_forward(p, pl, L, cf, m->post, m->fwd, nullptr, m->status, stream);
+      if (rc == I2C_OK) rc = run_backward(p, pl, L, cb, m->fwd, m->xm, m->post, m->zpost, m->cell_stats, m->term_stats, m->status, stream, no_mstep(m->term_stats));
       if (rc == I2C_OK && m->tau > 0 && it == 0) rc = to_feedback(p, m->tau, stream);  // (idempotent within a step: _update_priors)
     }
     if (rc != I2C_OK) return rc;

@@ -6,7 +6,9 @@ what the model runs by default ("G": the model's group width). T: default the ho
 inference and storage each take a comma-separated list: every combination runs in this one process. A request the engine refuses
 prints one "refused" line. Exit status 1 if any line differs; the last line counts lines, refusals and differences.
 I2C_AB_LIB=<lib.so>: the library compared against (default: the in-tree build); I2C_AB_NO_WORK=1: run without the chunk workspace;
-I2C_AB_PER_TRAJ=1: pass per-trajectory model parameters (models that have parameters)."""
+I2C_AB_PER_TRAJ=1: pass per-trajectory model parameters (models that have parameters); I2C_AB_LEARN=1: the four EM iterations by ONE
+i2c_learn call (eng.learn(4): the M-step on the reduction kernels, deferred into the next forward sweep, the helper wave) instead of
+four learn_msgs(), which never enter it."""
 import importlib
 import itertools
 import os
@@ -60,8 +62,11 @@ def run(lib, mode, B, lanes, T, inference, storage, x0, mu_u):
         eng.work = eng._problem.work = None
         if eng.cell_stats is None:
             eng.cell_stats = torch.zeros(T, 2, B, dtype=eng.dtype, device=eng.device)
-    for _ in range(4):
-        eng.learn_msgs()
+    if os.environ.get("I2C_AB_LEARN"):
+        eng.learn(4)
+    else:
+        for _ in range(4):
+            eng.learn_msgs()
     if eng.post.is_cuda:
         torch.cuda.synchronize()
     return eng.post.clone(), eng.alpha.clone(), eng.zpost.clone() if eng.zpost is not None else None, eng.backward_schedule
