@@ -709,8 +709,9 @@ template <typename R, typename S = R> struct FwdArgs {
 // bits). The wait for this wave's stores (vmcnt(0)) is the release; "memory" keeps the compiler's accesses on their side of it.
 // That is enough where the waves of a workgroup share one CU and its vector L1 (the default; the kernel is NOT built for threadgroup-
 // split mode, where the two waves could sit on different CUs and the release would have to write back / invalidate as well).
-// The contraction is the compiler's choice: the device cases of tests/test_forward_helper.py (torch.equal against k_forward) are what
-// holds it across compiler versions.
+// The contraction is the compiler's choice: the device cases of tests/test_forward_helper.py (torch.equal against k_forward; the LEAN
+// cell) and of tests/test_learn_general_variants.py (the general cell: weights that do not sum to one, per-cell targets, a moved
+// ring) are what holds it across compiler versions.
 struct NoRelease {
   static constexpr bool ON = false;
   int chunk_len;

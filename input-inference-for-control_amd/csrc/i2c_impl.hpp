@@ -947,9 +947,10 @@ static bool chunk_four_passes() {
   return e && atoi(e) == 4;
 }
 // Diagnostic knob (not part of the ABI), read where it reports: I2C_TRACE_PLAN=1 writes to stderr what a call dispatches beyond what
-// the plan's exports report -- at the launch of a lane forward sweep "i2c_forward_lane: sweep=<helper|plain>", in the chunked schedule
-// "i2c_backward_chunked: compose=<skipped|launched>" (tests/test_forward_helper.py reads them: the helper wave's composites and a
-// compose launch's are the same bytes in the same place).
+// the plan's exports report -- at the launch of a lane forward sweep "i2c_forward_lane: sweep=<helper|plain> lean=<0|1>" (the
+// compile-time variant of the sweep), in the chunked schedule "i2c_backward_chunked: compose=<skipped|launched> walk=<self|plain>
+// lean=<0|1>" (the walker and its variant). tests/test_forward_helper.py reads them -- the helper wave's composites and a compose
+// launch's are the same bytes in the same place --, tests/test_learn_general_variants.py that the general variants ran.
 static bool plan_trace() {
   const char* e = getenv("I2C_TRACE_PLAN");
   return e && atoi(e) == 1;
@@ -1441,7 +1442,7 @@ template <class M, typename R, typename S = R> struct Impl {
         if (pl.rule == I2C_INF_GAUSS_HERMITE) return launch(k_forward<M, R, false, true>, p->B, 1, LANE_BLOCK, stream, c, a, LANE_BLOCK);
       }
       const bool lean = c.rule_xu.unit && c.rule_x.unit && !c.z_per_cell && !a.alpha_cell && !a.prior_out && c.t0 == 0;
-      if (plan_trace()) fprintf(stderr, "i2c_forward_lane: sweep=%s\n", L.helper ? "helper" : "plain");
+      if (plan_trace()) fprintf(stderr, "i2c_forward_lane: sweep=%s lean=%d\n", L.helper ? "helper" : "plain", (int)lean);
       return lean ? launch_forward_lane<true>(p, L, c, a, pend, stream) : launch_forward_lane<false>(p, L, c, a, pend, stream);
     }
     return I2C_ENOTSUP;
@@ -1532,7 +1533,9 @@ template <class M, typename R, typename S = R> struct Impl {
       const bool lin = !MIXED && pl.rule == I2C_INF_LINEARIZE, gh = !MIXED && pl.rule == I2C_INF_GAUSS_HERMITE;
       const bool self = L.self_stitch;
       // compose
-      if (plan_trace()) fprintf(stderr, "i2c_backward_chunked: compose=%s\n", L.helper ? "skipped" : "launched");
+      if (plan_trace())
+        fprintf(stderr, "i2c_backward_chunked: compose=%s walk=%s lean=%d\n", L.helper ? "skipped" : "launched", self ? "self" : "plain",
+                (int)L.walk_lean);
       if (L.helper) {
         rc = I2C_OK;
       } else if (pl.compose == I2C_FAMILY_QUAD) {
