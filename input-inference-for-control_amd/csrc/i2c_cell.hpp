@@ -196,9 +196,14 @@ template <int DIN> struct DenseStruct {
 // Sin (2 wi sf^2 = 1 for every alpha, beta, kappa) and cost nothing.
 // Trig of the model's angle coordinates is computed once at the mean and once per (angle, column)
 // offset d = sf L[i][j], then rotated: sin(m +/- d) = s0 cd +/- c0 sd, cos(m +/- d) = c0 cd -/+ s0 sd.
-template <class M, class ST, int DIN, int DOUT, bool CROSS, bool UNITW = false, typename R, class F>
+// HANDOFF (a dense callback with CROSS only: every output moves with every column): Sxy is not formed. It receives the differences
+// themselves, Sxy[j * DOUT + k] = dl_j[k] -- DIN * DOUT values, the cross-covariance's own count -- and whoever takes them forms
+// wi sf L [dl_0 .. dl_{d-1}]^T from them and the factor (gain_from_handoff: the forward sweep's helper wave).
+template <class M, class ST, int DIN, int DOUT, bool CROSS, bool UNITW = false, bool HANDOFF = false, typename R, class F>
 I2C_FN void sp_transform(const Rule<R>& rule, const R* m, const R* Sin, const R* L, const F& f, R* my, R* Sy,
                          R* Sxy, const PolyTab<R>* tab = nullptr) {
+  static_assert(!HANDOFF || (CROSS && ST::lin(0) < 0 && ST::dep(0) == DIN - 1 && ST::lin(DOUT - 1) < 0 && ST::dep(DOUT - 1) == DIN - 1),
+                "the hand-off of the differences is the dense callback's");
   constexpr int NA = M::NA, NA1 = NA > 0 ? NA : 1;
   R s0[NA1], c0[NA1];
 #pragma unroll
@@ -215,7 +220,7 @@ I2C_FN void sp_transform(const Rule<R>& rule, const R* m, const R* Sin, const R*
   for (int k = 0; k < DOUT; ++k) A[k] = R(0);
 #pragma unroll
   for (int k = 0; k < sym(DOUT); ++k) Sy[k] = R(0);
-  if (CROSS) {
+  if (CROSS && !HANDOFF) {
 #pragma unroll
     for (int k = 0; k < DIN * DOUT; ++k) Sxy[k] = R(0);
   }
@@ -281,7 +286,8 @@ I2C_FN void sp_transform(const Rule<R>& rule, const R* m, const R* Sin, const R*
         if (nl_k && nl_l) Sy[tri(k, l)] += a[k] * a[l];
         if (d_k && d_l && !both_lin) Sy[tri(k, l)] += dl[k] * dl[l];
       }
-      if (CROSS && nl_k) {
+      if (CROSS && HANDOFF) Sxy[j * DOUT + k] = dl[k];
+      if (CROSS && !HANDOFF && nl_k) {
 #pragma unroll
         for (int i = j; i < DIN; ++i) Sxy[i * DOUT + k] += L[tri(i, j)] * dl[k];
       }
@@ -300,7 +306,7 @@ I2C_FN void sp_transform(const Rule<R>& rule, const R* m, const R* Sin, const R*
       else
         Sy[tri(k, l)] = hw * Sy[tri(k, l)] - w2 * A[k] * A[l];
     }
-    if (CROSS) {
+    if (CROSS && !HANDOFF) {
 #pragma unroll
       for (int i = 0; i < DIN; ++i)
         Sxy[i * DOUT + k] = ST::lin(k) >= 0 ? Sin[tri_any(i, ST::lin(k) >= 0 ? ST::lin(k) : 0)] : cs * Sxy[i * DOUT + k];
@@ -665,9 +671,10 @@ template <int GRID> I2C_FN void grid_read_before_write() {
 template <class M, int DIN, int DOUT, bool CROSS, typename R, class F>
 I2C_FN void grid_transform_wave(const Rule<R>& rule, const R* m, const R* L, const F& f, R* my, R* Sy, R* Sxy);  // i2c_grid.hpp
 
-template <int GRID, class M, class ST, int DIN, int DOUT, bool CROSS, bool UNITW = false, typename R, class F>
+template <int GRID, class M, class ST, int DIN, int DOUT, bool CROSS, bool UNITW = false, bool HANDOFF = false, typename R, class F>
 I2C_FN void transform(const Rule<R>& rule, const R* m, const R* Sin, const R* L, const F& f, R* my, R* Sy, R* Sxy,
                       const PolyTab<R>* tab = nullptr) {
+  static_assert(!HANDOFF || GRID == 0, "the hand-off of the differences is the sigma-point rule's (sp_transform)");
   if constexpr (GRID == GRID_WAVE) {
     grid_transform_wave<M, DIN, DOUT, CROSS>(rule, m, L, f, my, Sy, Sxy);
   } else if constexpr (GRID != 0) {
@@ -678,7 +685,7 @@ I2C_FN void transform(const Rule<R>& rule, const R* m, const R* Sin, const R* L,
     }
     grid_transform<M, DIN, DOUT, CROSS>(rule, m, L, f, my, Sy, Sxy);
   } else
-    sp_transform<M, ST, DIN, DOUT, CROSS, UNITW>(rule, m, Sin, L, f, my, Sy, Sxy, tab);
+    sp_transform<M, ST, DIN, DOUT, CROSS, UNITW, HANDOFF>(rule, m, Sin, L, f, my, Sy, Sxy, tab);
 }
 
 
@@ -712,14 +719,22 @@ template <typename R, typename S = R> struct FwdArgs {
 // The contraction is the compiler's choice: the device cases of tests/test_forward_helper.py (torch.equal against k_forward; the LEAN
 // cell) and of tests/test_learn_general_variants.py (the general cell: weights that do not sum to one, per-cell targets, a moved
 // ring) are what holds it across compiler versions.
+// GAIN (ChunkReleaseGain: k_forward_helper<GAINH>, fp64-stored messages): the helper also finishes the smoother gain J = sig_xy
+// sig_x3^-1 of every cell it composes -- J is only stored by the sweep, never read by it, so neither it nor sig_xy is on the carried
+// chain. The sweep then hands over, in J's own d nx slots of the row, the differences dl_j[k] of the dynamics transform (sp_transform
+// <HANDOFF>) and forms neither sig_xy nor J; the helper re-forms chol(sig_xu1_f), sig_xy, chol(sig_x3_f) and the solves from the row
+// with the sweep's expressions in the sweep's order (gain_from_handoff) and stores J over the hand-off. On the flagged cell J is
+// solved with the factor of sig_x3 BEFORE the terminal update while the row holds the one after it: there the sweep copies the earlier
+// one to term_sig [sym NX][B] (rows of the chunk workspace that are dead while the sweep runs: forward_helper_lane, i2c_impl.hpp),
+// inside the terminal block it has anyway.
 struct NoRelease {
-  static constexpr bool ON = false;
+  static constexpr bool ON = false, GAIN = false;
   int chunk_len;
   I2C_HD inline void release() const {}
   I2C_HD inline void release_if(int, int) const {}
 };
 struct ChunkRelease {
-  static constexpr bool ON = true;
+  static constexpr bool ON = true, GAIN = false;
   int chunk_len;  // ChunkArgs::chunk_len, wave-uniform
   I2C_HD inline void release() const {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -738,6 +753,13 @@ struct ChunkRelease {
     (void)t, (void)at;
 #endif
   }
+};
+template <typename R> struct ChunkReleaseGain {
+  static constexpr bool ON = true, GAIN = true;
+  int chunk_len;
+  R* term_sig;  // [sym NX][B]: sig_x3 of the flagged cell before its terminal update
+  I2C_HD inline void release() const { ChunkRelease{chunk_len}.release(); }
+  I2C_HD inline void release_if(const int t, const int at) const { ChunkRelease{chunk_len}.release_if(t, at); }
 };
 
 // LEAN = the common case fixed at compile time (weights sum to 1, shared target, trajectory-level alpha, no
@@ -984,7 +1006,8 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
 #pragma unroll
       for (int i = 0; i < sym(D); ++i) L[i] = S0[i];
       cell_bad = flag_stage(cell_bad, chol<D>(L, rinv), 3);
-      transform<GRID, M, DenseStruct<D>, D, NX, true, LEAN>(c.rule_xu, mu0, S0, L, DynamicsF<M, R>{params_of(c, b)}, mu_x, sig_x, Sxy, tab);
+      // (REL::GAIN: Sxy takes the hand-off dl_j[k] and stays it; the helper wave forms sig_xy and J)
+      transform<GRID, M, DenseStruct<D>, D, NX, true, LEAN, REL::GAIN>(c.rule_xu, mu0, S0, L, DynamicsF<M, R>{params_of(c, b)}, mu_x, sig_x, Sxy, tab);
     }
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) sig_x[i] += CONST_V ? eta_v[i] : (LEAN ? c.sig_eta[i + kz] : c.sig_eta_w[i + kz]);  // sum_p w_p sig_eta (quadrature.py:57)
@@ -993,11 +1016,13 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
     for (int i = 0; i < sym(NX); ++i) L3[i] = sig_x[i];
     cell_bad = flag_stage(cell_bad, chol<NX>(L3, rinv3), 4);
     sched_fence<(D >= 6)>();
+    if constexpr (!REL::GAIN) {
 #pragma unroll
-    for (int i = 0; i < D; ++i) {  // J = sig_xy sig_x3^{-1}, row by row
-      fsub<NX>(L3, rinv3, &Sxy[i * NX]);
-      bsub<NX>(L3, rinv3, &Sxy[i * NX]);
-      sched_fence<(D >= 6)>();
+      for (int i = 0; i < D; ++i) {  // J = sig_xy sig_x3^{-1}, row by row
+        fsub<NX>(L3, rinv3, &Sxy[i * NX]);
+        bsub<NX>(L3, rinv3, &Sxy[i * NX]);
+        sched_fence<(D >= 6)>();
+      }
     }
 
     // gfx9 counts loads AND stores in one counter (vmcnt). A wait on the prefetched prior rows placed (by the compiler)
@@ -1037,6 +1062,12 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
     if (NZT > 0 && t == c.terminal_cell && c.has_Qf) {
       constexpr int NT = C::NZT1;
       R mzt[NT], Szt[sym(NT)], Sxzt[NX * NT];
+      if constexpr (REL::GAIN) {  // the helper solves this cell's J with the factor of sig_x3 as it is HERE (see ChunkReleaseGain)
+        if (wr) {
+#pragma unroll
+          for (int i = 0; i < sym(NX); ++i) rel.term_sig[(unsigned long)i * B + b] = sig_x[i];
+        }
+      }
       transform<GRID, M, TermStruct<M>, NX, NT, true, LEAN>(c.rule_x, mu_x, sig_x, L3, ObserveTermF<M, R>{params_of(c, b)}, mzt, Szt, Sxzt);
 #pragma unroll
       for (int i = 0; i < sym(NT); ++i) Szt[i] += alpha * c.sig_xiT0[i];
@@ -1672,6 +1703,137 @@ I2C_HD inline void chunk_compose_body(const Consts<M, R>& c, const ChunkArgs<R, 
   for (int i = 0; i < NX * NX; ++i) out[(long)(NX + i) * B] = G[i];
 #pragma unroll
   for (int i = 0; i < sym(NX); ++i) out[(long)(NX + NX * NX + i) * B] = Cc[i];
+}
+
+// The smoother gain of one cell from the forward sweep's hand-off (ChunkReleaseGain): J holds the differences dl_j[k] of the dynamics
+// transform on entry, J = sig_xy sig_x3^-1 [D][NX] on return. S_xu1: sig_xu1_f of the row; S_x3: sig_x3 as the sweep factored it.
+// The expressions are the sweep's own, in its order -- chol<D> of section 3, the accumulation and the scaling of sp_transform<CROSS>,
+// chol<NX>, fsub and bsub per row --, so that the gain is the bits forward_sweep_body stores without the hand-off.
+template <class M, typename R> I2C_FN void gain_from_handoff(const Rule<R>& rule, const R* S_xu1, const R* S_x3, R* J) {
+  constexpr int NX = M::NX, D = M::NX + M::NU;
+  R L[sym(D)], rinv[D], Sxy[D * NX];
+#pragma unroll
+  for (int i = 0; i < sym(D); ++i) L[i] = S_xu1[i];
+  chol<D>(L, rinv);
+#pragma unroll
+  for (int k = 0; k < D * NX; ++k) Sxy[k] = R(0);
+#pragma unroll
+  for (int j = 0; j < D; ++j)
+#pragma unroll
+    for (int k = 0; k < NX; ++k)
+#pragma unroll
+      for (int i = j; i < D; ++i) Sxy[i * NX + k] += L[tri(i, j)] * J[j * NX + k];
+  const R cs = rule.wi * rule.sf;
+#pragma unroll
+  for (int k = 0; k < NX; ++k)
+#pragma unroll
+    for (int i = 0; i < D; ++i) Sxy[i * NX + k] = cs * Sxy[i * NX + k];
+  R L3[sym(NX)], rinv3[NX];
+#pragma unroll
+  for (int i = 0; i < sym(NX); ++i) L3[i] = S_x3[i];
+  chol<NX>(L3, rinv3);
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    fsub<NX>(L3, rinv3, &Sxy[i * NX]);
+    bsub<NX>(L3, rinv3, &Sxy[i * NX]);
+  }
+#pragma unroll
+  for (int k = 0; k < D * NX; ++k) J[k] = Sxy[k];
+}
+
+// chunk_compose_body behind a sweep that hands the gain over (ChunkReleaseGain; fp64-stored messages): every cell's J is finished from
+// its row (gain_from_handoff), stored over the hand-off, and composed from registers -- the composition itself is chunk_compose_body's,
+// expression for expression. The rows are fetched a cell ahead as there, so the solves sit under the load round trip of the next row.
+// term_sig: the flagged cell's sig_x3 before its terminal update (any t: a receding horizon flags a cell mid-horizon); the source of
+// a cell's sig_x3 is chosen by address, without a branch.
+template <class M, typename R>
+I2C_HD inline void chunk_compose_gain_body(const Consts<M, R>& c, const ChunkArgs<R, R>& a, const R* term_sig, const int ch, const int b) {
+  using C = Consts<M, R>;
+  constexpr int NX = C::NX, D = C::D;
+  constexpr int O_MU3 = D + sym(D), O_S3 = O_MU3 + NX, O_J = O_S3 + sym(NX);
+  const long B = c.B;
+  const int t_lo = ch * a.chunk_len, t_hi = (t_lo + a.chunk_len < c.T) ? t_lo + a.chunk_len : c.T;
+  const int t_term = (C::NZT > 0 && c.has_Qf) ? c.terminal_cell : -1;
+  R av[NX], G[NX * NX], Cc[sym(NX)];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) av[i] = R(0);
+#pragma unroll
+  for (int i = 0; i < NX; ++i)
+#pragma unroll
+    for (int j = 0; j < NX; ++j) G[i * NX + j] = i == j ? R(1) : R(0);
+#pragma unroll
+  for (int i = 0; i < sym(NX); ++i) Cc[i] = R(0);
+  struct Row {
+    R mu1[NX], S1[sym(D)], m3f[NX], S3f[sym(NX)], S3g[sym(NX)], J[D * NX];
+  };
+  auto load = [&](int t, Row& r) {
+    const R* in = a.cell.fwd + ((long)t * C::E_FWD) * B + b;
+    const R* s3 = t == t_term ? term_sig + b : in + (long)O_S3 * B;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) r.mu1[i] = in[(long)i * B];
+#pragma unroll
+    for (int i = 0; i < sym(D); ++i) r.S1[i] = in[(long)(D + i) * B];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) r.m3f[i] = in[(long)(O_MU3 + i) * B];
+#pragma unroll
+    for (int i = 0; i < sym(NX); ++i) r.S3f[i] = in[(long)(O_S3 + i) * B];
+#pragma unroll
+    for (int i = 0; i < sym(NX); ++i) r.S3g[i] = s3[(long)i * B];
+#pragma unroll
+    for (int i = 0; i < D * NX; ++i) r.J[i] = in[(long)(O_J + i) * B];
+  };
+  Row cur, nxt;
+  load(t_hi - 1, cur);
+  for (int t = t_hi - 1; t >= t_lo; --t) {
+    load(t > t_lo ? t - 1 : t_lo, nxt);  // one cell ahead, without a branch (the last one re-reads this row: unused)
+    gain_from_handoff<M, R>(c.rule_xu, cur.S1, cur.S3g, cur.J);
+    R* out = const_cast<R*>(a.cell.fwd) + ((long)t * C::E_FWD + O_J) * B + b;
+#pragma unroll
+    for (int i = 0; i < D * NX; ++i) out[(long)i * B] = cur.J[i];
+    R Jx[NX * NX];
+#pragma unroll
+    for (int i = 0; i < NX * NX; ++i) Jx[i] = opaque(cur.J[i]);  // as loaded values: the composition contracts as chunk_compose_body's
+    const R* mu1 = cur.mu1;
+    const R* S1 = cur.S1;  // (the xx block is the packed prefix)
+    const R* m3f = cur.m3f;
+    R S3n[sym(NX)];
+#pragma unroll
+    for (int i = 0; i < sym(NX); ++i) S3n[i] = Cc[i] - cur.S3f[i];  // C - sig_x3_f
+    // a <- mu1 + Jx (a - m3f);  C <- S1 + Jx (C - S3f) Jx^T;  G <- Jx G
+    R an[NX], Gn[NX * NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      R v = mu1[i];
+#pragma unroll
+      for (int k = 0; k < NX; ++k) v += Jx[i * NX + k] * (av[k] - m3f[k]);
+      an[i] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < sym(NX); ++i) Cc[i] = S1[i];
+    add_JDJt<NX, NX>(Jx, S3n, Cc);
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+      for (int j = 0; j < NX; ++j) {
+        R v = R(0);
+#pragma unroll
+        for (int k = 0; k < NX; ++k) v += Jx[i * NX + k] * G[k * NX + j];
+        Gn[i * NX + j] = v;
+      }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) av[i] = an[i];
+#pragma unroll
+    for (int i = 0; i < NX * NX; ++i) G[i] = Gn[i];
+    cur = nxt;
+  }
+  constexpr int EC = NX + NX * NX + sym(NX);
+  R* comp = a.comp + ((long)ch * EC) * B + b;
+#pragma unroll
+  for (int i = 0; i < NX; ++i) comp[(long)i * B] = av[i];
+#pragma unroll
+  for (int i = 0; i < NX * NX; ++i) comp[(long)(NX + i) * B] = G[i];
+#pragma unroll
+  for (int i = 0; i < sym(NX); ++i) comp[(long)(NX + NX * NX + i) * B] = Cc[i];
 }
 
 // One step of the stitch recursion: the smoothed state (m, S) that enters a chunk pushed through that chunk's composite map,

@@ -342,10 +342,30 @@ I2C_KERNEL(LANE_BLOCK) k_forward_mstep(I2C_LANE_PARAMS const Consts<M, R> c, con
 // for bit, and the backward sweep that follows starts with its walk. Both waves take the chunk geometry from the same argument and
 // meet at the barrier n_chunks times; nothing is exchanged through flags in memory. (Every wave has a live lane: the grid covers B.)
 // Host simulation: a lane's sweep, then its chunks -- a valid schedule, compose reads only finished rows.
-template <class M, typename R, bool LEAN, typename S, bool MSTEP>
+// GAINH (fp64-stored messages; Launches::helper_gain): wave 0 hands the smoother gain over as well (ChunkReleaseGain, i2c_cell.hpp) and
+// wave 1 finishes it cell by cell inside its compose loop (chunk_compose_gain_body). The flagged cell's sig_x3 travels through the
+// first sym(NX) rows of the per-chunk cost sums `part` [NC][3][B] of the chunk workspace, which are dead while a sweep of i2c_learn
+// runs: the pending M-step has read them in this kernel's prologue, lane b its own column b as here, and the walk behind the sweep
+// writes every one of them again before anything reads them (Impl::launches keeps the variant to 3 NC >= sym(NX)).
+template <class M, typename R, bool LEAN, typename S, bool MSTEP, bool GAINH>
 I2C_FN void forward_helper_lane(const Consts<M, R>& c, const FwdArgs<R, S>& a, const ChunkArgs<R, S>& ch, const PendingMstep<R>& pm,
                                 const int role, const int b) {
-  if (role == 0) {
+  if constexpr (GAINH) {
+    static_assert(sizeof(S) == sizeof(R), "the gain hand-off is not rounded to a narrower storage type");
+    R* const term_sig = ch.part;
+    if (role == 0) {
+      if constexpr (MSTEP) finish_pending_mstep<M, R>(c, pm, b);
+      forward_sweep_body<M, R, LEAN, 0, S, ChunkReleaseGain<R>>(c, a, b, ChunkReleaseGain<R>{ch.chunk_len, term_sig});
+    } else {
+      for (int k = 0; k < ch.n_chunks; ++k) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#endif
+        chunk_compose_gain_body<M, R>(c, ch, term_sig, k, b);
+      }
+    }
+  } else if (role == 0) {
     if constexpr (MSTEP) finish_pending_mstep<M, R>(c, pm, b);
     forward_sweep_body<M, R, LEAN, 0, S, ChunkRelease>(c, a, b, ChunkRelease{ch.chunk_len});
   } else {
@@ -370,14 +390,14 @@ constexpr int HELPER_WAVES = 2;
   const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / LANE_BLOCK));     \
   if (b < c.B)
 #endif
-template <class M, typename R, bool LEAN, typename S = R>
+template <class M, typename R, bool LEAN, typename S = R, bool GAINH = false>
 I2C_KERNEL(2 * LANE_BLOCK) k_forward_helper(I2C_LANE_PARAMS const Consts<M, R> c, const FwdArgs<R, S> a, const ChunkArgs<R, S> ch) {
-  I2C_HELPER_LANES forward_helper_lane<M, R, LEAN, S, false>(c, a, ch, PendingMstep<R>{}, role, (int)b);
+  I2C_HELPER_LANES forward_helper_lane<M, R, LEAN, S, false, GAINH>(c, a, ch, PendingMstep<R>{}, role, (int)b);
 }
-template <class M, typename R, bool LEAN, typename S = R>
+template <class M, typename R, bool LEAN, typename S = R, bool GAINH = false>
 I2C_KERNEL(2 * LANE_BLOCK) k_forward_mstep_helper(I2C_LANE_PARAMS const Consts<M, R> c, const FwdArgs<R, S> a, const ChunkArgs<R, S> ch,
                                                   const PendingMstep<R> pm) {
-  I2C_HELPER_LANES forward_helper_lane<M, R, LEAN, S, true>(c, a, ch, pm, role, (int)b);
+  I2C_HELPER_LANES forward_helper_lane<M, R, LEAN, S, true, GAINH>(c, a, ch, pm, role, (int)b);
 }
 #undef I2C_HELPER_LANES
 
@@ -947,10 +967,11 @@ static bool chunk_four_passes() {
   return e && atoi(e) == 4;
 }
 // Diagnostic knob (not part of the ABI), read where it reports: I2C_TRACE_PLAN=1 writes to stderr what a call dispatches beyond what
-// the plan's exports report -- at the launch of a lane forward sweep "i2c_forward_lane: sweep=<helper|plain> lean=<0|1>" (the
-// compile-time variant of the sweep), in the chunked schedule "i2c_backward_chunked: compose=<skipped|launched> walk=<self|plain>
-// lean=<0|1>" (the walker and its variant). tests/test_forward_helper.py reads them -- the helper wave's composites and a compose
-// launch's are the same bytes in the same place --, tests/test_learn_general_variants.py that the general variants ran.
+// the plan's exports report -- at the launch of a lane forward sweep "i2c_forward_lane: sweep=<helper|plain> lean=<0|1>
+// gain=<helper|sweep>" (the compile-time variant of the sweep, and which wave solves the smoother gains), in the chunked schedule
+// "i2c_backward_chunked: compose=<skipped|launched> walk=<self|plain> lean=<0|1>" (the walker and its variant).
+// tests/test_forward_helper.py reads them -- the helper wave's composites and a compose launch's are the same bytes in the same
+// place --, tests/test_learn_general_variants.py that the general variants ran, tests/test_forward_gain_helper.py who solved the gains.
 static bool plan_trace() {
   const char* e = getenv("I2C_TRACE_PLAN");
   return e && atoi(e) == 1;
@@ -992,6 +1013,10 @@ I2C_MODEL_CONST(bwd_fused_min_b, BWD_FUSED_MIN_B, I2C_BWD_FUSED_MIN_B)
 // batch size from which the forward sweep of i2c_learn composes the chunks on a helper wave (Impl::launches); see
 // ModelDefaults (i2c_models.hpp) for the measurement behind the default
 I2C_MODEL_CONST(forward_helper_min_b, FORWARD_HELPER_MIN_B, 4096)
+// does that helper wave also solve the smoother gains by default (Launches::helper_gain)? Measured (profiles/forward_gain_helper_ab.txt):
+// the pendulum (d = 3) gains 10 us per iteration at B = 4096, the cartpole (d = 5: the helper re-factors a 5 x 5 matrix per cell
+// and the sweep waits for it) loses 14 us there and 57 us at B = 8192; d = 4 is not measured and stays off
+I2C_MODEL_CONST(forward_helper_gain, FORWARD_HELPER_GAIN, M::NX + M::NU <= 3)
 // batch window in which the d <= 8 quad backward sweep is the model's DEFAULT; models without the pair: on request only
 I2C_MODEL_CONST(quad_backward_min_b, QUAD_BACKWARD8_MIN_B, 0)
 I2C_MODEL_CONST(quad_backward_max_b, QUAD_BACKWARD8_MAX_B, -1)
@@ -1039,6 +1064,7 @@ struct Launches {
   const int schedule;      // the backward schedule that RUNS: the plan's, or its fall-back without a workspace (Impl::schedule_with)
   const bool self_stitch;  // chunked: the walkers compute their boundary states themselves -- two launches, no stitch pass
   const bool helper;       // i2c_learn: the lane forward sweep composes the chunks on a helper wave, the chunked schedule starts with its walk
+  const bool helper_gain;  // ... and the helper wave finishes the smoother gains, which the sweep only hands over (fp64-stored messages)
   const bool defer;        // i2c_learn: the next forward sweep finishes the reduction and the M-step of every iteration but the call's last
   const bool reduces;      // the backward sweep ends in a reduction kernel (or defers it): the M-step of an iteration rides on that
   const bool walk_lean;    // the lane walkers, fused and chunked, write no optional output (see chunk_walk_body)
@@ -1394,7 +1420,14 @@ template <class M, typename R, typename S = R> struct Impl {
     const bool reduces = pl.backward == I2C_FAMILY_WAVE   ? mode == I2C_BWD_TWO_PASS && xm && cell_stats
                          : pl.backward == I2C_FAMILY_LANE ? mode != I2C_BWD_FUSED
                                                           : chunked;
-    return Launches{mode, self, helper, lane_forward && self, reduces, I2C_WALK_LEAN && !xm && !zpost && !cell_stats && !c.z_per_cell};
+    // I2C_FORWARD_HELPER_GAIN=0: the helper composes only and the sweep solves its gains itself (the reference of
+    // tests/test_forward_gain_helper.py and of the A/B timing); any other value: the helper solves them also for a model whose default
+    // is the sweep (forward_helper_gain)
+    const char* const eg = getenv("I2C_FORWARD_HELPER_GAIN");
+    int n_chunks, chunk_len;
+    chunk_geometry(p->B, p->T, &n_chunks, &chunk_len);
+    const bool helper_gain = helper && !MIXED && 3 * n_chunks >= sym(C::NX) && (eg ? strcmp(eg, "0") != 0 : forward_helper_gain<M>::value != 0);
+    return Launches{mode, self, helper, helper_gain, lane_forward && self, reduces, I2C_WALK_LEAN && !xm && !zpost && !cell_stats && !c.z_per_cell};
   }
 
   // ---- the sweeps: each written once for either storage type, dispatched from the plan and the call's Launches ---------------------
@@ -1407,6 +1440,11 @@ template <class M, typename R, typename S = R> struct Impl {
       if (L.helper) {
         constexpr int W = HELPER_WAVES;
         const ChunkArgs<R, S> ch = chunk_args<M>(p, CellArgs<R, S>{a.fwd});  // (the compose pass reads the forward messages only)
+        if constexpr (!MIXED) {
+          if (L.helper_gain)
+            return pend.part ? launch(k_forward_mstep_helper<M, R, LEAN, S, true>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, ch, pend)
+                             : launch(k_forward_helper<M, R, LEAN, S, true>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, ch);
+        }
         return pend.part ? launch(k_forward_mstep_helper<M, R, LEAN, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, ch, pend)
                          : launch(k_forward_helper<M, R, LEAN, S>, W * (long)p->B, 1, W * LANE_BLOCK, stream, c, a, ch);
       }
@@ -1442,7 +1480,8 @@ template <class M, typename R, typename S = R> struct Impl {
         if (pl.rule == I2C_INF_GAUSS_HERMITE) return launch(k_forward<M, R, false, true>, p->B, 1, LANE_BLOCK, stream, c, a, LANE_BLOCK);
       }
       const bool lean = c.rule_xu.unit && c.rule_x.unit && !c.z_per_cell && !a.alpha_cell && !a.prior_out && c.t0 == 0;
-      if (plan_trace()) fprintf(stderr, "i2c_forward_lane: sweep=%s lean=%d\n", L.helper ? "helper" : "plain", (int)lean);
+      if (plan_trace())
+        fprintf(stderr, "i2c_forward_lane: sweep=%s lean=%d gain=%s\n", L.helper ? "helper" : "plain", (int)lean, L.helper_gain ? "helper" : "sweep");
       return lean ? launch_forward_lane<true>(p, L, c, a, pend, stream) : launch_forward_lane<false>(p, L, c, a, pend, stream);
     }
     return I2C_ENOTSUP;

@@ -47,6 +47,8 @@ struct ModelDefaults {
   // T = 200 (profiles/forward_helper_other_legs.txt): B = 4096 (16 chunks of 13 cells) 0.3458 -> 0.3394 ms per iteration; B = 1024
   // (29 chunks of 7) 0.3170 -> 0.3177; B = 1 0.3531 -> 0.3694, T = 100 (25 chunks of 4) 0.1831 -> 0.1901: with chunks that short
   // the sweep waits for the helper at the barrier. Not measured between 1024 and 4096, nor from 4097 to the fused walk's batch.
+  // (optional) static constexpr int FORWARD_HELPER_GAIN: 1 / 0, whether that helper wave also solves the smoother gains, which the sweep
+  // then only hands over (fp64-stored messages; forward_helper_gain, i2c_impl.hpp); models without it: 1 where nx + nu <= 3
   I2C_HD static constexpr int ang(int) { return 0; }
   // structure hints of the observation functions (ObsStruct, i2c_cell.hpp): output k is a pass-through of input obs_lin(k), or
   // (-1) a general function that depends on no input with an index above obs_dep(k). The defaults say "nothing is known"
