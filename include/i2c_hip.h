@@ -226,7 +226,13 @@ typedef struct I2cProblem {
   /* I2C_INF_GAUSS_HERMITE: numpy.polynomial.hermite.hermgauss(gh_degree) nodes and weights (exp_types.py:57) */
   double gh_nodes[I2C_MAX_GH_DEGREE], gh_weights[I2C_MAX_GH_DEGREE];
   /* HOST constants (double, packed lower where symmetric) */
-  double sig_eta[I2C_SYM(I2C_MAX_NX)];   /* sys.sig_eta                                          */
+  double sig_eta[I2C_SYM(I2C_MAX_NX)];   /* sys.sig_eta: the CONSTANT part of the one-step covariance. A model whose functor has the
+                                          * optional process_noise member adds Q(x, u) per sigma point: a point's covariance is
+                                          * sig_eta + Q(x_p, u_p), summed with the rule's covariance weights (one-lane kernels, sigma-
+                                          * point rule; everything else is I2C_ENOTSUP for such a model). For the sweeps sig_eta may
+                                          * then be zero; the sampling calls (i2c_rollout, i2c_plant_step, i2c_mpc_episode with eps_x)
+                                          * still want it positive definite, and factor sig_eta + Q(x, u) in the lane at every step:
+                                          * a step whose sum is not positive definite leaves that lane's state NaN.               */
   double sig_xi0[I2C_SYM(I2C_MAX_NZ)];   /* inv(QR)   (i2c.py:786)  -> sig_xi = alpha * sig_xi0  */
   double QR[I2C_SYM(I2C_MAX_NZ)];        /* blkdiag(Q, R) (i2c.py:781-784)                       */
   double sig_xiT0[I2C_SYM(I2C_MAX_NZ)];  /* inv(Qf)   (i2c.py:789)                               */

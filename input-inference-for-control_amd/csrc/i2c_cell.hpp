@@ -150,6 +150,48 @@ template <class M, typename R> struct DynamicsFixedUF {
     }
   }
 };
+// OPTIONAL member of a functor: the state-action-dependent part of the one-step covariance at the point xu (same arguments and
+// operation set as dynamics), so that the covariance of a point is sig_eta + Q(xu) -- the reference's `sys.forward(x_pts) -> (means, one
+// covariance PER POINT)`, summed with the rule's covariance weights by its consumers (quadrature.py:46-58, mpc.py:131-137):
+//   template <typename R> I2C_FN void process_noise(const R* p, const R* xu, const R* sn, const R* cs, R* q);  // q[sym(NX)], packed lower
+// Detected, never required: a model without it compiles to what it compiled to before the member existed.
+template <class M, typename R, typename = void> struct has_process_noise : std::false_type {};
+template <class M, typename R>
+struct has_process_noise<M, R, std::void_t<decltype(M::template process_noise<R>((const R*)nullptr, (const R*)nullptr, (const R*)nullptr,
+                                                                                 (const R*)nullptr, (R*)nullptr))>> : std::true_type {};
+// Q at one point, parameters as the callbacks above take them
+template <class M, typename R> I2C_FN void process_noise_at(const ParamSrc<M, R>& p, const R* xu, const R* sn, const R* cs, R* q) {
+  if constexpr (is_per_traj<M>::value) {
+    R pb[M::NP];
+    M::process_noise(param_ptr<M::NP>(p, pb), xu, sn, cs, q);
+  } else {
+    M::process_noise(p, xu, sn, cs, q);
+  }
+}
+// The dynamics of such a model inside a sigma-point transform: sp_transform evaluates noise() at every point it evaluates the
+// callback at -- the point and its sines / cosines exist there -- and leaves sum_p w_p Q(x_p) in q[sym(NX)] (centre point with the
+// weight w0, which general weights may make negative; then the pairs in column order, times wi).
+template <class M, typename R> struct DynamicsNoiseF : DynamicsF<M, R> {
+  static constexpr int NQ = sym(M::NX);
+  R* q;
+  I2C_HD inline void noise(const R* x, const R* sn, const R* cs, R* qp) const { process_noise_at<M, R>(this->p, x, sn, cs, qp); }
+};
+// ... and with a known action appended (CKF prediction): Q(x_p, u)
+template <class M, typename R> struct DynamicsFixedUNoiseF : DynamicsFixedUF<M, R> {
+  static constexpr int NQ = sym(M::NX);
+  R* q;
+  I2C_HD inline void noise(const R* x, const R* sn, const R* cs, R* qp) const {
+    R xu[M::NX + M::NU];
+#pragma unroll
+    for (int i = 0; i < M::NX; ++i) xu[i] = x[i];
+#pragma unroll
+    for (int i = 0; i < M::NU; ++i) xu[M::NX + i] = this->u[i];
+    process_noise_at<M, R>(this->p, xu, sn, cs, qp);
+  }
+};
+template <class F, typename = void> struct carries_noise : std::false_type {};
+template <class F> struct carries_noise<F, std::void_t<decltype(F::NQ)>> : std::true_type {};
+
 template <class M, typename R> struct ObserveTermF {
   ParamSrc<M, R> p;
   I2C_HD inline void operator()(const R* x, const R* sn, const R* cs, R* y) const {
@@ -215,6 +257,15 @@ I2C_FN void sp_transform(const Rule<R>& rule, const R* m, const R* Sin, const R*
   }
   R y0[DOUT];
   f(m, s0, c0, y0);
+  // (a functor that carries a point-dependent noise term, DynamicsNoiseF: Q at the centre, then the sum over the pairs)
+  constexpr bool NOISE = carries_noise<F>::value;
+  static_assert(!NOISE || (!HANDOFF && ST::lin(0) < 0 && ST::dep(0) == DIN - 1), "a noise term rides on a dense callback, whose every column is evaluated");
+  R q0[NOISE ? sym(DOUT) : 1], qs[NOISE ? sym(DOUT) : 1];
+  if constexpr (NOISE) {
+    f.noise(m, s0, c0, q0);
+#pragma unroll
+    for (int i = 0; i < sym(DOUT); ++i) qs[i] = R(0);
+  }
   R A[DOUT];
 #pragma unroll
   for (int k = 0; k < DOUT; ++k) A[k] = R(0);
@@ -266,6 +317,13 @@ I2C_FN void sp_transform(const Rule<R>& rule, const R* m, const R* Sin, const R*
       R yp[DOUT], ym[DOUT];
       f(xp, sp, cp, yp);
       f(xm, sm, cm, ym);
+      if constexpr (NOISE) {
+        R qp[sym(DOUT)], qm[sym(DOUT)];
+        f.noise(xp, sp, cp, qp);
+        f.noise(xm, sm, cm, qm);
+#pragma unroll
+        for (int i = 0; i < sym(DOUT); ++i) qs[i] += qp[i] + qm[i];
+      }
 #pragma unroll
       for (int k = 0; k < DOUT; ++k) {
         a[k] = (yp[k] - y0[k]) + (ym[k] - y0[k]);
@@ -295,6 +353,10 @@ I2C_FN void sp_transform(const Rule<R>& rule, const R* m, const R* Sin, const R*
     sched_fence<(DIN >= 6)>();
   }
   const R hw = R(0.5) * rule.wi, w2 = rule.wi * rule.wi, cs = rule.wi * rule.sf;
+  if constexpr (NOISE) {
+#pragma unroll
+    for (int i = 0; i < sym(DOUT); ++i) f.q[i] = rule.w0 * q0[i] + rule.wi * qs[i];
+  }
 #pragma unroll
   for (int k = 0; k < DOUT; ++k) {
     const R Wk = UNITW ? R(1) : rule.W;
@@ -1001,16 +1063,26 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
     // ---- 3. dynamics push-through (i2c.py:415-421) and smoother gain (i2c.py:423-425) --
     sched_fence<(D >= 6)>();
     R Sxy[D * NX];
+    constexpr bool NOISE = GRID == 0 && has_process_noise<M, R>::value;
+    static_assert(!NOISE || !REL::ON, "a model with process_noise runs the plain sweep (Impl::launches)");
+    [[maybe_unused]] R qn[NOISE ? sym(NX) : 1];
     {
       R L[sym(D)], rinv[D];
 #pragma unroll
       for (int i = 0; i < sym(D); ++i) L[i] = S0[i];
       cell_bad = flag_stage(cell_bad, chol<D>(L, rinv), 3);
       // (REL::GAIN: Sxy takes the hand-off dl_j[k] and stays it; the helper wave forms sig_xy and J)
-      transform<GRID, M, DenseStruct<D>, D, NX, true, LEAN, REL::GAIN>(c.rule_xu, mu0, S0, L, DynamicsF<M, R>{params_of(c, b)}, mu_x, sig_x, Sxy, tab);
+      if constexpr (NOISE)
+        transform<GRID, M, DenseStruct<D>, D, NX, true, LEAN>(c.rule_xu, mu0, S0, L, DynamicsNoiseF<M, R>{{params_of(c, b)}, qn}, mu_x, sig_x, Sxy, tab);
+      else
+        transform<GRID, M, DenseStruct<D>, D, NX, true, LEAN, REL::GAIN>(c.rule_xu, mu0, S0, L, DynamicsF<M, R>{params_of(c, b)}, mu_x, sig_x, Sxy, tab);
     }
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) sig_x[i] += CONST_V ? eta_v[i] : (LEAN ? c.sig_eta[i + kz] : c.sig_eta_w[i + kz]);  // sum_p w_p sig_eta (quadrature.py:57)
+    if constexpr (NOISE) {  // ... + sum_p w_p Q(x_p): the model's point-dependent part (has_process_noise)
+#pragma unroll
+      for (int i = 0; i < sym(NX); ++i) sig_x[i] += qn[i];
+    }
     R L3[sym(NX)], rinv3[NX];
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) L3[i] = sig_x[i];
@@ -2235,9 +2307,16 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
     sum_m += cm;
     sum_v += cv;
 
-    transform<GRID, M, DenseStruct<D>, D, NX, false>(c.rule_xu, mu0, S0, L0, DynamicsF<M, R>{params_of(c, b)}, mu_x, sig_x, (R*)nullptr);
+    if constexpr (GRID == 0 && has_process_noise<M, R>::value) {  // sum_p w_p (sig_eta + Q(x_p))
+      R qn[sym(NX)];
+      transform<GRID, M, DenseStruct<D>, D, NX, false>(c.rule_xu, mu0, S0, L0, DynamicsNoiseF<M, R>{{params_of(c, b)}, qn}, mu_x, sig_x, (R*)nullptr);
 #pragma unroll
-    for (int i = 0; i < sym(NX); ++i) sig_x[i] += c.sig_eta_w[i];
+      for (int i = 0; i < sym(NX); ++i) sig_x[i] += c.sig_eta_w[i] + qn[i];
+    } else {
+      transform<GRID, M, DenseStruct<D>, D, NX, false>(c.rule_xu, mu0, S0, L0, DynamicsF<M, R>{params_of(c, b)}, mu_x, sig_x, (R*)nullptr);
+#pragma unroll
+      for (int i = 0; i < sym(NX); ++i) sig_x[i] += c.sig_eta_w[i];
+    }
     if (wr) {
 #pragma unroll
       for (int e = 0; e < NX; ++e) out[(long)(D + sym(D) + e) * B] = mu_x[e];
@@ -2323,10 +2402,18 @@ I2C_HD inline void ckf_filter_body(const Consts<M, R>& c, const R* sig_zeta, con
   bool ok = chol<NX>(L, rinv);
   // prediction (mpc.py:129-137): x-only sigma points, the action is appended unchanged
   R mf[NX], Sf[sym(NX)];
-  sp_transform<M, DenseStruct<NX>, NX, NX, false>(c.rule_x, mu, S, L, DynamicsFixedUF<M, R>{params_of(c, b), u}, mf, Sf,
-                                                  (R*)nullptr);
+  if constexpr (has_process_noise<M, R>::value) {  // sum_p w_p (sig_eta + Q(x_p, u)), the applied action fixed
+    R qn[sym(NX)];
+    sp_transform<M, DenseStruct<NX>, NX, NX, false>(c.rule_x, mu, S, L, DynamicsFixedUNoiseF<M, R>{{params_of(c, b), u}, qn}, mf, Sf,
+                                                    (R*)nullptr);
 #pragma unroll
-  for (int i = 0; i < sym(NX); ++i) L[i] = Sf[i] = Sf[i] + c.rule_x.W * c.sig_eta[i];
+    for (int i = 0; i < sym(NX); ++i) L[i] = Sf[i] = Sf[i] + c.rule_x.W * c.sig_eta[i] + qn[i];
+  } else {
+    sp_transform<M, DenseStruct<NX>, NX, NX, false>(c.rule_x, mu, S, L, DynamicsFixedUF<M, R>{params_of(c, b), u}, mf, Sf,
+                                                    (R*)nullptr);
+#pragma unroll
+    for (int i = 0; i < sym(NX); ++i) L[i] = Sf[i] = Sf[i] + c.rule_x.W * c.sig_eta[i];
+  }
   ok = chol<NX>(L, rinv) && ok;
   // innovation (mpc.py:139-145): K = sig_xy sig_y^{-1}; mu = mu_f + K (y - mu_y); cov = sig_f - K sig_y K^T
   R my[NY], Sy[sym(NY)], Sxy[NX * NY];
@@ -2348,6 +2435,16 @@ I2C_HD inline void ckf_filter_body(const Consts<M, R>& c, const R* sig_zeta, con
 // b), T sequential steps; the disturbance samples are supplied by the caller as standard normals so
 // that a rollout is a deterministic function of its inputs.
 // ------------------------------------------------------------------------------------------
+// Le = chol(sig_eta + Q(xu)) of a model with process_noise (the sampling kernels); false: not positive definite
+template <class M, typename R> I2C_FN bool step_noise_factor(const R* sig_eta, const R* prm, const R* xu, const R* sn, const R* cs, R* Le) {
+  constexpr int NX = M::NX;
+  R q[sym(NX)], rinv[NX];
+  M::process_noise(prm, xu, sn, cs, q);
+#pragma unroll
+  for (int i = 0; i < sym(NX); ++i) Le[i] = sig_eta[i] + q[i];
+  return chol<NX>(Le, rinv);
+}
+
 template <typename R> struct RolloutArgs {
   const R* post;     // [T][E_POST][B]  posterior + controller written by the backward sweep
   const R* x0;       // [NX][B]
@@ -2387,7 +2484,7 @@ I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, 
 #pragma unroll
       for (int j = 0; j <= i; ++j) x[i] += L[tri(i, j)] * a.eps_x0[(long)j * N + n];
   }
-  R Le[sym(NX)], rinv_e[NX];  // chol(sig_eta), constant
+  R Le[sym(NX)], rinv_e[NX];  // chol(sig_eta), constant (a model with process_noise: refactored at every step)
 #pragma unroll
   for (int i = 0; i < sym(NX); ++i) Le[i] = c.sig_eta[i];
   if (a.eps_x) chol<NX>(Le, rinv_e);
@@ -2457,10 +2554,20 @@ I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, 
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = xn[i];
     if (a.eps_x) {
+      if constexpr (has_process_noise<M, R>::value) {  // x' = f(x, u) + chol(sig_eta + Q(x, u)) eps, factored in the lane at every step
+        const bool ok = step_noise_factor<M, R>(c.sig_eta, prm, xu, sn, cs, Le);
 #pragma unroll
-      for (int i = 0; i < NX; ++i)
+        for (int i = 0; i < NX; ++i)
 #pragma unroll
-        for (int j = 0; j <= i; ++j) x[i] += Le[tri(i, j)] * a.eps_x[((long)t * NX + j) * N + n];
+          for (int j = 0; j <= i; ++j) x[i] += Le[tri(i, j)] * a.eps_x[((long)t * NX + j) * N + n];
+#pragma unroll
+        for (int i = 0; i < NX; ++i) x[i] = ok ? x[i] : R(__builtin_nan(""));  // (not positive definite: this rollout's state is NaN from here on)
+      } else {
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+#pragma unroll
+          for (int j = 0; j <= i; ++j) x[i] += Le[tri(i, j)] * a.eps_x[((long)t * NX + j) * N + n];
+      }
     }
   }
   if (a.x_final) {
@@ -2552,10 +2659,21 @@ I2C_HD inline void plant_step_body(const Consts<M, R>& c, const PlantNoise<M, R>
     R e[NX];
 #pragma unroll
     for (int j = 0; j < NX; ++j) e[j] = a.eps_x[(long)j * B + b];
+    if constexpr (has_process_noise<M, R>::value) {  // chol(sig_eta + Q(x, u)) of this step, factored in the lane
+      R Le[sym(NX)];
+      const bool ok = step_noise_factor<M, R>(c.sig_eta, prm, xu, sn, cs, Le);
 #pragma unroll
-    for (int i = 0; i < NX; ++i)
+      for (int i = 0; i < NX; ++i)
 #pragma unroll
-      for (int j = 0; j <= i; ++j) xn[i] += nz.Le[tri(i, j)] * e[j];
+        for (int j = 0; j <= i; ++j) xn[i] += Le[tri(i, j)] * e[j];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xn[i] = ok ? xn[i] : R(__builtin_nan(""));
+    } else {
+#pragma unroll
+      for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) xn[i] += nz.Le[tri(i, j)] * e[j];
+    }
   }
 #pragma unroll
   for (int i = 0; i < NX; ++i) a.x[(long)i * B + b] = xn[i];

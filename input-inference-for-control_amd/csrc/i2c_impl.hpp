@@ -1074,16 +1074,21 @@ template <class M, typename R, typename S = R> struct Impl {
   using C = Consts<M, R>;
   static constexpr bool MIXED = sizeof(S) != sizeof(R);
   static constexpr int G = M::GROUP;
-  static constexpr bool HAS_GROUP = G > 0 && sizeof(R) == 8 && !MIXED;
+  // A model with the optional process_noise member (state-action-dependent process noise, i2c_cell.hpp) is served by the one-lane
+  // kernels under the sigma-point rule and, for its forward sweep, by the d <= 8 quad kernels (whose backward passes read what the
+  // forward sweep stored and need nothing): no other multi-lane family is instantiated for it, none is its default, and a request
+  // for one, for Linearize() / Gauss-Hermite or for the Riccati messages is I2C_ENOTSUP (those forms of the term do not exist).
+  static constexpr bool NOISE = has_process_noise<M, R>::value;
+  static constexpr bool HAS_GROUP = G > 0 && sizeof(R) == 8 && !MIXED && !NOISE;
   static constexpr bool LANE = !M::GROUP_ONLY;  // one-lane-per-trajectory kernels exist
-  static constexpr bool HAS_WAVE = M::WAVE && sizeof(R) == 8;  // fp64 matrix instruction; the storage type S may be float
-  static constexpr bool HAS_QUAD = M::QUAD && sizeof(R) == 8;  // fp64 matrix instruction (i2c_quad.hpp): forward sweep; the storage type S may be float
+  static constexpr bool HAS_WAVE = M::WAVE && sizeof(R) == 8 && !NOISE;  // fp64 matrix instruction; the storage type S may be float
+  static constexpr bool HAS_QUAD = M::QUAD && sizeof(R) == 8 && !(NOISE && QG<M>::WIDE);  // fp64 matrix instruction (i2c_quad.hpp): forward sweep; the storage type S may be float
   static constexpr bool WIDE = QG<M>::WIDE;                    // the d = 16 form of the quad kernels
   static constexpr bool HAS_QUAD_BACKWARD = HAS_QUAD && quad_backward_exists<M>();  // ... and the backward sweep
   static constexpr bool QUAD8 = HAS_QUAD_BACKWARD && !WIDE && LANE;  // d <= 8: the fused quad walk, and the quad passes of the chunked schedule
   static constexpr bool HAS_QUAD_CKF = HAS_QUAD && !MIXED && quad_ckf_exists<M>();  // the filter step of the d = 16 form
   static constexpr bool HAS_QUAD_PROP = HAS_QUAD && !MIXED && quad_propagate_exists<M>();  // the closed-loop propagation of the d = 16 form
-  static constexpr bool HAS_GRID = LANE && sizeof(R) == 8 && !MIXED;  // the grid kernels run the one-lane bodies: wherever those exist, fp64
+  static constexpr bool HAS_GRID = LANE && sizeof(R) == 8 && !MIXED && !NOISE;  // the grid kernels run the one-lane bodies: wherever those exist, fp64
 
   // ---- the resolver -------------------------------------------------------------------------------------------------------------
   // I2cProblem.group_lanes, normalised once against what the model has; nothing below reads the field again
@@ -1100,6 +1105,10 @@ template <class M, typename R, typename S = R> struct Impl {
   static Request request(const int lanes, const int inference) {
     if (lanes == 0) return REQ_DEFAULT;
     if (lanes == -1) return REQ_ONE_LANE;
+    if constexpr (NOISE) {  // the quad kernels by either name, nothing else
+      if (HAS_QUAD && (lanes == 64 || lanes == I2C_LANES_QUAD)) return lanes == 64 ? REQ_QUAD : REQ_QUAD_FORWARD;
+      return REQ_NOT_OURS;
+    }
     if (lanes == 64 && HAS_GRID && inference == I2C_INF_GAUSS_HERMITE) return REQ_GRID;
     if (lanes == 64 && (M::WAVE || M::QUAD)) return HAS_WAVE ? REQ_WAVE : (HAS_QUAD ? REQ_QUAD : REQ_DEFAULT);
     if (lanes == I2C_LANES_QUAD) return HAS_QUAD ? (WIDE ? REQ_QUAD : REQ_QUAD_FORWARD) : REQ_DEFAULT;
@@ -1338,6 +1347,13 @@ template <class M, typename R, typename S = R> struct Impl {
     const Request req = request(p->group_lanes, p->inference);
     Plan pl;
     pl.rule = p->inference;
+    if constexpr (NOISE) {
+      if (p->inference != I2C_INF_CUBATURE) {
+        pl.forward = pl.backward = pl.propagate = pl.filter = pl.schedule = pl.walker = pl.compose = pl.stitch = I2C_ENOTSUP;
+        pl.fwd_tm = pl.fusable = false;
+        return pl;
+      }
+    }
     pl.forward = forward_family(p, req, unit);
     pl.backward = backward_family(p, req, unit);
     pl.propagate = propagate_family(p, req, unit_xu || p->inference == I2C_INF_LINEARIZE);
@@ -1354,7 +1370,7 @@ template <class M, typename R, typename S = R> struct Impl {
     }
     // (the fp32-storage path has never set the flag)
     pl.fwd_tm = !MIXED && pl.forward == I2C_FAMILY_QUAD && ((M::WAVE && pl.backward == I2C_FAMILY_WAVE) || (HAS_QUAD_BACKWARD && pl.backward == I2C_FAMILY_QUAD));
-    pl.fusable = LANE && C::D <= 5 && p->inference == I2C_INF_CUBATURE && pl.forward == I2C_FAMILY_LANE && pl.propagate == I2C_FAMILY_LANE &&
+    pl.fusable = !NOISE && LANE && C::D <= 5 && p->inference == I2C_INF_CUBATURE && pl.forward == I2C_FAMILY_LANE && pl.propagate == I2C_FAMILY_LANE &&
                  rule_xu.unit && rule_x.unit && !(p->z_per_cell && p->z) && !p->alpha_cell && p->t0 == 0;
     return pl;
   }
@@ -1411,7 +1427,7 @@ template <class M, typename R, typename S = R> struct Impl {
     const bool two_launch = SELF_STITCH && chunked && pl.rule == I2C_INF_CUBATURE && !c.has_x_terminal && !chunk_four_passes();
     const bool self = two_launch && pl.stitch == I2C_FAMILY_LANE && pl.walker == I2C_FAMILY_LANE;
     const bool lane_forward = in_learn && two_launch && pl.forward == I2C_FAMILY_LANE;
-    bool helper = lane_forward && pl.compose == I2C_FAMILY_LANE && LANE_BLOCK == 64 && sweep_lanes() == LANE_BLOCK;
+    bool helper = !NOISE && lane_forward && pl.compose == I2C_FAMILY_LANE && LANE_BLOCK == 64 && sweep_lanes() == LANE_BLOCK;
     if (helper) {
       const char* e = getenv("I2C_FORWARD_HELPER");
       helper = e ? strcmp(e, "0") != 0 : p->B >= forward_helper_min_b<M>::value;
@@ -1427,7 +1443,7 @@ template <class M, typename R, typename S = R> struct Impl {
     int n_chunks, chunk_len;
     chunk_geometry(p->B, p->T, &n_chunks, &chunk_len);
     const bool helper_gain = helper && !MIXED && 3 * n_chunks >= sym(C::NX) && (eg ? strcmp(eg, "0") != 0 : forward_helper_gain<M>::value != 0);
-    return Launches{mode, self, helper, helper_gain, lane_forward && self, reduces, I2C_WALK_LEAN && !xm && !zpost && !cell_stats && !c.z_per_cell};
+    return Launches{mode, self, helper, helper_gain, !NOISE && lane_forward && self, reduces, I2C_WALK_LEAN && !xm && !zpost && !cell_stats && !c.z_per_cell};
   }
 
   // ---- the sweeps: each written once for either storage type, dispatched from the plan and the call's Launches ---------------------
@@ -1436,7 +1452,7 @@ template <class M, typename R, typename S = R> struct Impl {
   template <bool LEAN>
   static int launch_forward_lane(const I2cProblem* p, const Launches& L, const C& c, const FwdArgs<R, S>& a, const PendingMstep<R>& pend, void* stream) {
     const int lanes = sweep_lanes();
-    if constexpr (SELF_STITCH) {
+    if constexpr (SELF_STITCH && !NOISE) {  // (process_noise: neither the helper wave nor the deferred M-step, Impl::launches)
       if (L.helper) {
         constexpr int W = HELPER_WAVES;
         const ChunkArgs<R, S> ch = chunk_args<M>(p, CellArgs<R, S>{a.fwd});  // (the compose pass reads the forward messages only)
@@ -1636,7 +1652,7 @@ template <class M, typename R, typename S = R> struct Impl {
 
   static int riccati(const I2cProblem* p, const void* prior_out, const void* fwd, const void* xm, void* post, void* ric,
                      int32_t* status, void* stream) {
-    if constexpr (MIXED) return I2C_ENOTSUP;
+    if constexpr (MIXED || NOISE) return I2C_ENOTSUP;  // (NOISE: the Riccati messages read the constant sig_eta alone)
     if constexpr (LANE) {
       if (!lane_request(p->group_lanes)) return I2C_ENOTSUP;
       const C c = make_consts<M, R>(p, 0.0, 0);
@@ -1710,7 +1726,7 @@ template <class M, typename R, typename S = R> struct Impl {
     for (int it = 0; it < n_iters; ++it) {
       int rc = I2C_OK;
       bool fused = false;
-      if constexpr (LANE && C::D <= 5) {
+      if constexpr (LANE && C::D <= 5 && !NOISE) {
         if (overlap && pl.fusable && pending >= 0) {  // (fusable: the sigma-point rule as given, so cp is the forward sweep's constants with use_expert)
           FwdArgs<R> af{(const R*)post, (R*)fwd, nullptr, (const R*)p->x0, (const R*)p->sig_x0, (const R*)p->z, (const R*)p->alpha,
                         (const R*)p->alpha_cell, p->feedforward, status, p->expert};

@@ -447,6 +447,46 @@ template <class M, typename R, int NOUT> struct ObserveHeadF {
   }
 };
 
+// The dynamics of a model with the optional process_noise member (i2c_cell.hpp) inside q_points, d <= 8 geometry: the lane that
+// evaluates point p also evaluates Q(x_p) from the same x, sn, cs and leaves its sym(NX) values in q (its OWN point's: q_noise_sum
+// weights and sums them over the trajectory's sixteen lanes); q0: Q at the centre where every lane evaluates it for itself (CENTRE).
+template <class M, typename R> struct QuadDynamicsNoiseF : DynamicsNoiseF<M, R> {
+  R* q0;
+};
+// sum_p w_p Q(x_p) over the points of one q_points<.., DIN, ..> pass, added to the upper blocks sx [NBX][NBX] of the predicted
+// covariance. Lane p holds Q of its point in ql: a pair row below DIN carries wi; a pair row beyond the input dimension is a centre
+// evaluation, and ONE of them (the + lane of the last pair row) carries the centre's weight w0 -- once, not once per spare row; with
+// no spare row the centre's Q is every lane's own qc (CENTRE) and needs no exchange. The exchange is in registers: a DPP sum over the
+// four lanes of a block row (q_rowsum), then the matrix instruction's sum over the four block rows (q_colsum) -- the same fixed order
+// for every trajectory slot of the wavefront, so a trajectory's result does not depend on its position in the batch. Every lane then
+// holds all sym(NX) sums and keeps the entries of its (row, column).
+template <class G, int DIN, int NX, bool CENTRE, typename R>
+I2C_FN void q_noise_sum(const Quad<R>& q, const Rule<R>& rule, const R* ql, const R* qc, R* sx) {
+  constexpr int NBX = (NX + 3) / 4, PR = G::PR;
+  static_assert(!G::WIDE, "process_noise: the d <= 8 geometry of the quad kernels");
+  const int p = q.p();
+  const R wl = (p & 7) < DIN ? rule.wi : ((DIN < PR && p == PR - 1) ? rule.w0 : R(0));
+  R tot[sym(NX)];
+#pragma unroll
+  for (int e = 0; e < sym(NX); ++e) {
+    R v = q_colsum(q, q_rowsum(q, wl * ql[e]));
+    if constexpr (CENTRE && DIN >= PR) v += rule.w0 * qc[e];
+    tot[e] = v;
+  }
+#pragma unroll
+  for (int i = 0; i < NBX; ++i)
+#pragma unroll
+    for (int j = i; j < NBX; ++j) {
+      R add = R(0);
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr)
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+          if (4 * i + rr < NX && 4 * j + kk < NX) add = (q.r == rr && q.c == kk) ? tot[tri_any(4 * i + rr, 4 * j + kk)] : add;
+      sx[i * NBX + j] += add;
+    }
+}
+
 // ---- sigma points ------------------------------------------------------------------------------------------------------------
 // The points m +/- sf L[:, p] of a DIN-dimensional rule through f, one evaluation per lane of the trajectory and pass
 // (d <= 8: lane p < 8: +, lane 8 + p: -, one pass; d <= 16: lane p: + in the first pass, - in the second; geometry G = QG<model>).
@@ -496,6 +536,7 @@ I2C_FN void q_points(const Quad<R>& q, const R sf, const R* muc, const R* lt, co
       else r_sincos(x[M::ang(k)], &sn[k], &cs[k]);
     }
     f(x, sn, cs, y);
+    if constexpr (carries_noise<F>::value) f.noise(x, sn, cs, f.q);  // Q at this lane's point (QuadDynamicsNoiseF; one pass: d <= 8)
     if (G::WIDE && pass == 1) q.sync();  // the second half of the results overwrites the directions: after their last read
     const int yrow = (G::WIDE ? pass * PR + p : p) * YLD;
 #pragma unroll
@@ -511,6 +552,7 @@ I2C_FN void q_points(const Quad<R>& q, const R sf, const R* muc, const R* lt, co
       else r_sincos(x[M::ang(k)], &sn[k], &cs[k]);
     }
     f(x, sn, cs, y);
+    if constexpr (carries_noise<F>::value) f.noise(x, sn, cs, f.q0);
 #pragma unroll
     for (int j = 0; j < NBO; ++j) {
       R v = R(0);
@@ -1329,13 +1371,19 @@ I2C_HD inline void forward_quad_body(const Consts<M, R>& c, const KC& kc, const 
       }
       I2C_QSTAMP(5);  // stores + chol(updated joint)
       R am[NBD * NBX], dm[NBD * NBX], yc[NBX], sy[NBX * NBX];
-      q_points<M, G, D, NX, CENTRE>(q, rule.sf, mu0, lt, DynamicsF<M, R>{params_of(c, b)}, am, dm, yc);
+      constexpr bool NOISE = has_process_noise<M, R>::value;
+      [[maybe_unused]] R qn[NOISE ? sym(NX) : 1], qn0[NOISE ? sym(NX) : 1];
+      if constexpr (NOISE)
+        q_points<M, G, D, NX, CENTRE>(q, rule.sf, mu0, lt, QuadDynamicsNoiseF<M, R>{{{params_of(c, b)}, qn}, qn0}, am, dm, yc);
+      else
+        q_points<M, G, D, NX, CENTRE>(q, rule.sf, mu0, lt, DynamicsF<M, R>{params_of(c, b)}, am, dm, yc);
       I2C_QSTAMP(6);  // dynamics points
       q_moments<D, NX, GENERAL>(q, rule, am, dm, yc, mx, sy);
 #pragma unroll
       for (int i = 0; i < NBX; ++i)
 #pragma unroll
         for (int j = 0; j < NBX; ++j) sx[i * NBX + j] = j >= i ? sy[i * NBX + j] + q_ldc<QLD>(q, kc.eta, i, j, kz) : R(0);
+      if constexpr (NOISE) q_noise_sum<G, D, NX, CENTRE>(q, rule, qn, qn0, sx);  // + sum_p w_p Q(x_p) (has_process_noise)
 #pragma unroll
       for (int k = 0; k < NBX * NBD; ++k) sxy[k] = R(0);
       q_tn<NBD, NBX, NBD, false, false, true>(q, dm, lt, sxy);  // sig_xy^T = wi sf [d_p]^T L^T

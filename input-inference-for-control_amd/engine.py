@@ -189,6 +189,32 @@ class BatchedI2c:
         if inference not in ("cubature", "linearize", "gauss_hermite"):
             raise ValueError(f"unknown inference method {inference!r}")
         self.inference = inference
+        # A model with state-action-dependent process noise (KnownModel.process_noise; the functor's process_noise member) is served by
+        # the one-lane kernels and the d <= 8 quad kernels under the sigma-point rule: the other forms of the term do not exist, and the library answers
+        # I2C_ENOTSUP for them (Impl::resolve) -- refused here, before anything is allocated.
+        # Whether the FUNCTOR has the member is the library's to say: asked here, of the resolver, before anything is allocated -- the
+        # state estimator's filter step under Linearize() is served for every model without the member (whatever kernels it has) and
+        # is I2C_ENOTSUP for every model with it. A Python object that overrides process_noise over a functor without the member
+        # (an in-tree model_id kept, say) would be solved with constant noise, silently: refused. The reverse -- a header with the
+        # member under a class without the override -- is a model with the term.
+        probe = _native.I2cProblem()
+        probe.abi_version, probe.model_id, probe.B, probe.T = _native.ABI_VERSION, self.model_id, 1, 1
+        probe.inference, probe.quad_alpha = _native.INF_LINEARIZE, 1.0
+        functor_has = self.lib.i2c_kernel_family(C.byref(probe), _native.SWEEP_FILTER) == -2  # I2C_ENOTSUP
+        if bool(getattr(model, "has_process_noise", False)) and not functor_has:
+            raise ValueError(f"{type(model).__name__} overrides process_noise, but its device functor (model id {self.model_id}) has no "
+                             "process_noise member: the kernels would solve it with constant noise (INTEGRATION.md section 3)")
+        self.has_process_noise = functor_has
+        if self.has_process_noise:
+            if dims.group_only:
+                raise ValueError("a model with process_noise needs the one-lane kernels (nx + nu <= 8): this one has group kernels only")
+            if inference != "cubature":
+                raise ValueError(f"inference={inference!r}: a model with process_noise is solved with the sigma-point rule (\"cubature\") only")
+            # (the d <= 8 quad kernels: the forward sweep sums the term over its lanes; fp64 arithmetic, as every quad kernel)
+            quad_ok = bool(dims.quad) and nx + nu <= 8 and dtype == torch.float64
+            if self.group_lanes not in (0, -1) + ((64, _native.LANES_QUAD) if quad_ok else ()):
+                raise ValueError(f"group_lanes={self.group_lanes}: a model with process_noise runs on the one-lane kernels (0 or -1)"
+                                 + (f" or the quad kernels (64 or {_native.LANES_QUAD})" if quad_ok else ""))
         self.linearize = inference == "linearize"
         self.gauss_hermite = inference == "gauss_hermite"
         self.gh_degree = 0

@@ -36,6 +36,11 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 GEN_DIR = os.path.join(PKG_DIR, "lib", "generated")
 
 FUNCTIONS = ("dynamics", "observe", "observe_terminal", "measure")
+# ... and the OPTIONAL fifth: the state-action-dependent part Q(xu) of the one-step covariance, sym(NX) packed-lower expressions of the
+# dynamics' inputs (the functor's optional process_noise member, csrc/i2c_cell.hpp). Traced only when the model gives it, with the
+# same operation sets and refusals; no Jacobian is emitted for it. A model without it emits the text it always did.
+PROCESS_NOISE = "process_noise"
+
 OPERATIONS = "sin, cos, exp, clip(x, lo, hi), rcp, pi and + - * / with integer powers"
 OPERATIONS_EXTENDED = ("sin, cos, exp, sqrt, tanh, log, abs, minimum, maximum, where_gt(a, b, x, y), clip(x, lo, hi), rcp, pi and "
                        "+ - * / with integer and half-integer powers")
@@ -49,6 +54,17 @@ BOOL_KNOBS = ("QUAD", "GROUP_FORWARD_AUTO")
 
 _ENV = None
 _ENV_LOCK = threading.Lock()
+
+
+def pack_lower(out, nx):
+    """sym(nx) packed-lower (row-major) entries from what a process_noise function returned: those entries themselves, or the full
+    nx x nx matrix as nx rows (lists or tuples of nx entries each), whose lower triangle is taken. Only the matrix form is recognised
+    here -- for nx = 1 that is `[[q]]`, while `[q]` is the packed form --; anything else is passed on as it is, and a wrong number
+    of entries (three flat entries for nx = 3, say) is refused by the caller's count check like any other function's."""
+    out = list(out)
+    if len(out) == nx and all(isinstance(r, (list, tuple)) and len(r) == nx for r in out):
+        return [out[i][j] for i in range(nx) for j in range(i + 1)]
+    return out
 
 
 def _env():
@@ -189,10 +205,11 @@ class Spec:
         self.general_sines = []  # the distinct arguments of the general sines (extended models), over all functions
 
     def n_in(self, fn):
-        return self.D if fn in ("dynamics", "observe") else self.NX
+        return self.D if fn in ("dynamics", "observe", PROCESS_NOISE) else self.NX
 
     def n_out(self, fn):
-        return {"dynamics": self.NX, "observe": self.NZ, "observe_terminal": self.NZT, "measure": self.NY}[fn]
+        return {"dynamics": self.NX, "observe": self.NZ, "observe_terminal": self.NZT, "measure": self.NY,
+                PROCESS_NOISE: self.NX * (self.NX + 1) // 2}[fn]
 
 
 def check_limits(dims, n_params, who="model"):
@@ -221,12 +238,15 @@ def trace(dims, fns, n_params, who="model", operations="basic"):
     ps = [sp.Symbol(f"p{i}", real=True) for i in range(spec.NP)]
     spec.xs, spec.ps = xs, ps
     raw = {}
-    for fn in FUNCTIONS:
+    functions = spec.functions = FUNCTIONS + ((PROCESS_NOISE,) if fns.get(PROCESS_NOISE) is not None else ())
+    for fn in functions:
         label = f"{who}.{fn}_fn"
         n_in, n_out = spec.n_in(fn), spec.n_out(fn)
         try:
             out = fns[fn](list(xs[:n_in]), list(ps), env.math_extended if ext else env.math)
             out = [] if out is None else list(out)
+            if fn == PROCESS_NOISE:
+                out = pack_lower(out, spec.NX)
         except (TypeError, AttributeError) as e:
             raise ValueError(f"{label}: {e} -- a Python branch, comparison or foreign function on a traced value cannot be compiled "
                              f"(the operation set is {ops})") from e
@@ -242,7 +262,7 @@ def trace(dims, fns, n_params, who="model", operations="basic"):
     ang = set()
     normal = {}
     general = set()
-    for fn in FUNCTIONS:
+    for fn in functions:
         if ext:  # (state inputs only: a sine of anything else is a general sine, not an error)
             normal[fn] = [_split_sines(_normalise(e), xs[:min(spec.n_in(fn), spec.NX)], ang, general) for e in raw[fn]]
         else:
@@ -258,7 +278,7 @@ def trace(dims, fns, n_params, who="model", operations="basic"):
         table[sp.sin(xs[j])] = spec.sn[a]
         table[sp.cos(xs[j])] = spec.cs[a]
     allowed = set(xs) | set(ps) | set(spec.sn) | set(spec.cs)
-    for fn in FUNCTIONS:
+    for fn in functions:
         spec.exprs[fn] = [e.xreplace(table) for e in normal[fn]]
         for k, e in enumerate(spec.exprs[fn]):
             _check_operations(e, allowed, f"{who}.{fn}_fn", k, ext)
@@ -645,6 +665,10 @@ def emit(spec, struct, jacobian=True, knobs=None, origin=None):
         n_in = spec.n_in(fn)
         body = _body(_names(spec, n_in), [], [(f"y[{k}]", e) for k, e in enumerate(spec.exprs[fn])])
         s.append(f"  template <typename R> I2C_FN void {fn}(const R* p, const R* x, const R* sn, const R* cs, R* y) {{\n{body}  }}\n")
+    if PROCESS_NOISE in spec.exprs:
+        body = _body(_names(spec, spec.D), [], [(f"q[{k}]", e) for k, e in enumerate(spec.exprs[PROCESS_NOISE])])
+        s.append("  // the state-action-dependent part of the one-step covariance at the point x = (state, action): q[sym(NX)], packed lower\n"
+                 f"  template <typename R> I2C_FN void {PROCESS_NOISE}(const R* p, const R* x, const R* sn, const R* cs, R* q) {{\n{body}  }}\n")
     if jacobian:
         s.append("  // value and Jacobian of one function (FN: 0 dynamics, 1 observe, 2 observe_terminal), Jac[k * DIN + j] = d y_k / d x_j\n"
                  "  template <int FN, typename R> I2C_FN void jacobian(const R* p, const R* x, const R* sn, const R* cs, R* y, R* Jac) {\n")

@@ -113,9 +113,21 @@ class KnownModel:
         other models observe their terminal features here (matches the device functor)."""
         return self.observe_terminal(x)
 
+    def process_noise(self, xu):
+        """The state-action-dependent part Q(xu), (P, nx, nx), of the one-step covariance: a point's covariance is sig_eta + Q(xu)
+        (the reference's `sys.forward(x_pts) -> (means, one covariance PER POINT)`). None: constant noise. A model that overrides it
+        names a device functor with the `process_noise` member: the kernels evaluate that one."""
+        return None
+
+    @property
+    def has_process_noise(self):
+        return type(self).process_noise is not KnownModel.process_noise
+
     def forward(self, xu):
         xn = self.dynamics(xu)
-        return xn, np.broadcast_to(self.sig_eta, (xu.shape[0],) + self.sig_eta.shape).copy()
+        cov = np.broadcast_to(self.sig_eta, (xu.shape[0],) + self.sig_eta.shape).copy()
+        q = self.process_noise(xu)
+        return xn, cov if q is None else cov + np.asarray(q, dtype=float)
 
     def __call__(self, xu):
         return self.forward(xu)

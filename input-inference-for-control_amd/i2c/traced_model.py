@@ -102,6 +102,16 @@ class TracedModel(KnownModel):
     def measure_fn(self, x, p, m):
         return self.observe_terminal_fn(x, p, m)
 
+    def process_noise_fn(self, xu, p, m):
+        """OPTIONAL: the state-action-dependent part Q(xu) of the one-step covariance (a point's covariance is sig_eta + Q(xu)): the
+        sym(nx) packed-lower (row-major) expressions, or the full nx x nx matrix as rows. Same operation set as dynamics_fn. A class
+        that does not override it has constant noise, and its device functor is the one it always was."""
+        return None
+
+    @property
+    def has_process_noise(self):
+        return type(self).process_noise_fn is not TracedModel.process_noise_fn
+
     @property
     def dim_y(self):
         """Number of outputs of measure_fn (counted once: it is a property of the class's functions)."""
@@ -141,6 +151,17 @@ class TracedModel(KnownModel):
     def measure(self, x):
         return self._numpy(self.measure_fn, x, self.dim_x, self.dim_y)
 
+    def process_noise(self, xu):
+        if not self.has_process_noise:
+            return None
+        nx = self.dim_x
+        packed = self._numpy(lambda v, p, m: _codegen().pack_lower(self.process_noise_fn(v, p, m), nx), xu, self.dim_xu, nx * (nx + 1) // 2)
+        r, c = np.tril_indices(nx)
+        q = np.zeros(packed.shape[:-1] + (nx, nx))
+        q[..., r, c] = packed
+        q[..., c, r] = packed
+        return q
+
     # ---- device side ----------------------------------------------------------------------------------------------------------
     def trace(self):
         """The traced expressions (functor_codegen.Spec); raises ValueError for anything a functor cannot hold."""
@@ -153,6 +174,8 @@ class TracedModel(KnownModel):
         dims["NY"] = self.dim_y
         fns = {"dynamics": self.dynamics_fn, "observe": self.observe_fn, "observe_terminal": self.observe_terminal_fn,
                "measure": self.measure_fn}
+        if self.has_process_noise:
+            fns["process_noise"] = self.process_noise_fn
         if self.operations == "basic":
             return cg, cg.trace(dims, fns, n_params, who)
         return cg, cg.trace(dims, fns, n_params, who, operations=self.operations)
