@@ -425,7 +425,8 @@ int i2c_shift_horizon(const I2cProblem* p, void* post, const void* cell_init, co
 /*
  * Riccati-form backward messages after a Linearize forward/backward pass: replaces I2cGraph._backward_ricatti_msgs
  * (i2c.py:888-893) over I2cCell._backward_ricatti_msgs (i2c.py:612-678), the verification helper of
- * scripts/lqr_compare.py:175. Requires p->inference == I2C_INF_LINEARIZE.
+ * scripts/lqr_compare.py:175. Requires p->inference == I2C_INF_LINEARIZE. p->alpha_cell, where set, is honoured as in the
+ * sweeps: sig_xi of cell t is alpha_cell[row t][b] * sig_xi0 (the lambda_z1_f, nu_z1_f, nu_z2_f the reference's forward pass stored).
  *   prior_out  [T][d+SYM(d)][B]  in: what i2c_forward_sweep wrote as `prior_out` (mu_xu0_f, sig_xu0_f)
  *   fwd        [T][e_fwd][B]     in
  *   xm         [T][e_xm][B]      in: what i2c_backward_sweep wrote (only cell T-1 is read)

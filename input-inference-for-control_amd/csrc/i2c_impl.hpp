@@ -1657,7 +1657,7 @@ template <class M, typename R, typename S = R> struct Impl {
       if (!lane_request(p->group_lanes)) return I2C_ENOTSUP;
       const C c = make_consts<M, R>(p, 0.0, 0);
       RiccatiArgs<R> a{(const R*)prior_out, (const R*)fwd, (const R*)xm, (const R*)p->z, (const R*)p->alpha,
-                       (R*)post,            (R*)ric,       status};
+                       (const R*)p->alpha_cell, (R*)post, (R*)ric, status};
       return launch(k_riccati<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
     }
     return I2C_ENOTSUP;

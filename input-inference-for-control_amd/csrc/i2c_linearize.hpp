@@ -690,7 +690,8 @@ I2C_HD inline void chunk_reduce_lin_body(const Consts<M, R>& c, const ChunkArgs<
 // sig_u2_f, sig_x2_f, lambda_x2_f, lambda_x3_f, nu_x3_f; :278-346) from the prior / forward buffers, then walks
 // T-1..0. Every matrix the reference inverts here is symmetric; they are inverted through their Cholesky factor and a
 // non-positive pivot (improper backward message, e.g. no terminal cost) flags the trajectory with I2C_FAIL_RICCATI.
-// Dense row-major N x N helpers; this path is a diagnostic, not a hot loop.
+// Each cell's sig_xi takes the cell's own temperature (I2cProblem.alpha_cell) where there is one, as the sweeps above do.
+// Dense row-major N x N helpers; this path is a diagnostic, not a hot loop. Tests: tests/test_riccati.py.
 // ------------------------------------------------------------------------------------------
 template <int N, typename R> I2C_FN bool spd_inverse(const R* A /* dense, symmetric */, R* Ainv /* dense */) {
   R L[sym(N)], rinv[N];
@@ -757,6 +758,7 @@ template <typename R> struct RiccatiArgs {
   const R* xm;      // [T][E_XM][B]        only cell T-1 is read (mu_x3_m, sig_x3_m at the end of the chain)
   const R* z;       // [T][NZ][B] or null
   const R* alpha;   // [B]
+  const R* alpha_cell;  // [T][B] ring, or null: the temperature of cell t's sig_xi instead of alpha[b] (I2cProblem.alpha_cell)
   R* post;          // [T][E_POST][B]      in: sig_u0_m; out: K, k, sigK overwritten with the Riccati-form controller
   R* ric;           // [T][NX + NX*NX][B]  out: nu_x0_b, lambda_x0_b (row-major)
   int32_t* status;
@@ -769,10 +771,10 @@ I2C_HD inline void riccati_body(const Consts<M, R>& c, const RiccatiArgs<R>& a, 
   constexpr int O_MU3 = D + sym(D), O_S3 = O_MU3 + NX, O_CTL = D + sym(D);
   const long B = c.B;
   const int T = c.T;
-  const R alpha = a.alpha[b];
   bool ok = true;
   R nu3b[NX], lam3b[NX * NX];
   for (int t = T - 1; t >= 0; --t) {
+    const R alpha = a.alpha_cell ? a.alpha_cell[(long)c.row(t) * B + b] : a.alpha[b];  // the cell's own sig_xi, as the sweeps above
     const R* pr = a.prior + ((long)t * (D + sym(D))) * B + b;
     const R* in = a.fwd + ((long)t * C::E_FWD) * B + b;
     R* po = a.post + ((long)c.row(t) * C::E_POST) * B + b;
