@@ -263,6 +263,35 @@ typedef struct I2cProblem {
                                  read column b (parameter i at i * B + b) in every sweep, filter step and rollout (rollout n:
                                  column n % B). I2C_EINVAL on a model with n_params = 0. Kernel families and backward schedules
                                  are the same as without it (i2c_kernel_family, i2c_backward_schedule).                    */
+  const int32_t* horizons;    /* optional [B] int32 (device): per-trajectory horizons. NULL (a zeroed problem): every trajectory has
+                                 horizon T, today's behaviour in every respect. Otherwise trajectory b consists of cells
+                                 0 .. T_b - 1, T_b = horizons[b], 1 <= T_b <= T, and its result is exactly what a solve of that
+                                 trajectory alone with horizon T_b computes. T stays the allocated number of rows of every
+                                 buffer; of the persistent inputs rows t >= T_b are never read, of the outputs rows t >= T_b are
+                                 never written. The kernels clamp what they read to [1, T]: a bad value cannot index outside a buffer.
+                                  - the terminal cost update (has_Qf) of trajectory b happens in its cell T_b - 1 (terminal_cell
+                                    must be T - 1, meaning "each trajectory's last cell", or -1: none);
+                                  - so does the end of the backward chain: the terminal observation, or the tempered terminal
+                                    state prior of covariance control;
+                                  - the M-step divides by nz T_b (+ nzt);
+                                  - term_stats, prop_stats (its KL row included), the rollout's x_final and z_term (rollout n:
+                                    the horizon of column n % B) refer to cell T_b - 1;
+                                  - status[b] carries the trajectory's own step index;
+                                  - the mode flags `feedforward` stay one [T] array for the batch; a trajectory of ONE cell
+                                    reads its cell as feed-forward whatever feedforward[0] says: the reference's graph of
+                                    horizon 1 has tau = horizon - 1 = 0 and never switches a cell (i2c.py:833, 1212). In
+                                    effect trajectory b's switch index is min(tau, T_b - 1).
+                                 Served by the one-lane kernels (forward, backward and propagate sweeps resolve to
+                                 I2C_FAMILY_LANE for group_lanes 0 and -1) in fp64 (I2C_F64) under the sigma-point rule
+                                 (I2C_INF_CUBATURE, any alpha, beta, kappa). The backward sweep has one schedule, the fused walk,
+                                 without a workspace: I2C_BWD_AUTO / _CHUNKED / _TWO_PASS are answered with I2C_BWD_FUSED. No helper
+                                 wave, no deferred M-step, no propagation overlap. Everything else is refused before any launch:
+                                 I2C_ENOTSUP for a group_lanes request for the group, wave, quad or grid kernels, a group_only
+                                 model, I2C_INF_LINEARIZE / _GAUSS_HERMITE, I2C_F32 / I2C_F64_F32S, a model with process_noise;
+                                 I2C_EINVAL for t0 != 0, alpha_cell != NULL, a terminal_cell other than T - 1 or -1, and from
+                                 i2c_mpc_step, i2c_shift_horizon, i2c_mpc_episode and i2c_riccati_sweep. i2c_ckf_filter and
+                                 i2c_plant_step do not read T and are unaffected. The resolvers (i2c_kernel_family,
+                                 i2c_backward_schedule) only test the pointer against NULL.                                    */
 } I2cProblem;
 
 /*

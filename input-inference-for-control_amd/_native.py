@@ -102,6 +102,7 @@ class I2cProblem(C.Structure):
         ("feedforward", C.c_void_p),
         ("expert", C.c_void_p),
         ("model_params_b", C.c_void_p),  # optional [NP][B] per-trajectory model parameters (arithmetic dtype)
+        ("horizons", C.c_void_p),  # optional [B] int32 per-trajectory horizons (NULL: every trajectory has horizon T)
     ]
 
 

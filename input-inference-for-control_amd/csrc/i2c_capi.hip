@@ -220,6 +220,7 @@ int i2c_riccati_sweep(const I2cProblem* p, const void* prior_out, const void* fw
                       int32_t* status, void* stream) {
   if (!prior_out || !fwd || !xm || !post || !ric || !status) return I2C_EINVAL;
   if (p && p->inference != I2C_INF_LINEARIZE) return I2C_EINVAL;
+  if (p && p->horizons) return I2C_EINVAL;  // per-trajectory horizons: the sigma-point EM path only
   I2C_DISPATCH(p, riccati(p, prior_out, fwd, xm, post, ric, status, stream));
 }
 
@@ -227,6 +228,7 @@ int i2c_mpc_step(const I2cProblem* p, const I2cMpcStep* m, void* stream) {
   if (!m || !m->post || !m->fwd || !m->term_stats || !m->cell_init || !m->status || m->n_iter < 0) return I2C_EINVAL;
   if (m->do_filter && (!m->y || !m->u)) return I2C_EINVAL;
   if (p && p->alpha_cell && !m->alpha_init) return I2C_EINVAL;
+  if (p && p->horizons) return I2C_EINVAL;  // the ring of the MPC loop has one horizon
   I2C_DISPATCH(p, mpc_step(p, m, stream));
 }
 
@@ -234,6 +236,7 @@ int i2c_shift_horizon(const I2cProblem* p, void* post, const void* cell_init, co
                       void* action, void* stream) {
   if (!post || !cell_init) return I2C_EINVAL;
   if (p && p->alpha_cell && !alpha_init) return I2C_EINVAL;
+  if (p && p->horizons) return I2C_EINVAL;
   I2C_DISPATCH(p, shift(p, post, cell_init, alpha_init, z_new, action, stream));
 }
 
@@ -306,6 +309,7 @@ int i2c_mpc_episode(const I2cProblem* p, const I2cMpcStep* m, I2cEpisode* ep, vo
   if (ep->observe_state && (ep->eps_y || ep->y_hist)) return I2C_EINVAL;  // nothing is measured in that mode
   if (p && p->alpha_cell && !m->alpha_init) return I2C_EINVAL;
   if (ep->z_traj && (ep->n_z < 1 || !p || !p->z_per_cell || !p->z)) return I2C_EINVAL;
+  if (p && p->horizons) return I2C_EINVAL;
   int rc = check_problem(p);
   if (rc != I2C_OK) return rc;
   const i2c::ModelOps* planner = find_ops(p->model_id, p->dtype);

@@ -827,13 +827,22 @@ template <typename R> struct ChunkReleaseGain {
 // LEAN = the common case fixed at compile time (weights sum to 1, shared target, trajectory-level alpha, no
 // joint-prior output): the corresponding wave-uniform runtime branches disappear from the cell, which keeps
 // it one scheduling region. The generic variant (LEAN = false) handles everything.
-template <class M, typename R, bool LEAN = false, int GRID = 0, typename ST_ = R, class REL = NoRelease>
-I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST_>& a, const int b, const REL rel = REL{0}) {
+// HZ (per-trajectory horizons, I2cProblem.horizons; generic variant, t0 = 0, no alpha_cell): the lane's loop runs to ITS horizon Tb
+// (clamp_horizon) and the terminal update fires in its cell Tb - 1. The time index stays ONE value for the lanes that are still
+// running -- a lane that is done leaves the loop, the others go on with the same t --, so the wave-uniform row offsets (make_window,
+// wld, uniform_u32) hold as they are. The one-cell-ahead fetches (prior rows, target, mode flag) name row t + 1, wave-uniform as
+// well, and a lane in its last cell takes no part in them: no row t >= Tb is read. The flag is compile-time and defaults to off:
+// every other instantiation compiles from the code it had.
+I2C_HD inline int clamp_horizon(const int h, const int T) { return h < 1 ? 1 : (h > T ? T : h); }
+template <class M, typename R, bool LEAN = false, int GRID = 0, typename ST_ = R, class REL = NoRelease, bool HZ = false>
+I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST_>& a, const int b, const REL rel = REL{0},
+                                      [[maybe_unused]] const int Tb = 0) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NU = C::NU, NZ = C::NZ, NZT = C::NZT, D = C::D;
   constexpr unsigned W = sizeof(ST_);
+  static_assert(!HZ || (!LEAN && GRID == 0 && !REL::ON), "per-trajectory horizons: the generic one-lane sweep on its own");
   const unsigned long B = c.B;
-  const int T = c.T;
+  const int T = HZ ? Tb : c.T;
   const unsigned bo = (unsigned)b * W;     // the lane's byte offset inside any row
   const unsigned rb0 = (unsigned)(B * W);  // bytes per row (wave-uniform)
   const R alpha_traj = a.alpha[b];
@@ -876,6 +885,9 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
   // vector load whose full latency (plus, vmcnt being shared, the acknowledgement of the previous cell's last stores)
   // is exposed EVERY cell. It is therefore fetched one cell ahead, together with the prior rows.
   unsigned ff_cur = a.ff[LEAN ? 0 : c.row(0)];
+  // (a trajectory of ONE cell never leaves feed-forward mode, whatever the batch's shared flag of cell 0 says: a graph of horizon 1
+  //  has tau = 0 and _update_priors switches nothing, i2c.py:833, 1212)
+  if constexpr (HZ) ff_cur = T == 1 ? 1u : ff_cur;
   // Small models never factor the prior joint: its Cholesky factor is assembled from the factor Lx of the incoming
   // sig_x0_f (= chol(sig_x3_f) of the previous cell, already needed for the smoother gain) as
   //   L0 = [[Lx, 0], [K~ Lx, chol(sig_u|x)]],  sig_u|x = sig_u0_m - K~ sig_ux^T   (feed-forward: K~ = 0, sig_u|x = sig_u0_f),
@@ -922,8 +934,10 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
 
   [[maybe_unused]] int next_release = rel.chunk_len;  // (REL) the first cell of the second chunk
   for (int t = 0; t < T; ++t) {
-    const int tn = t + 1 < T ? t + 1 : t;
-    const int tr = LEAN ? t : c.row(t), tnr = LEAN ? tn : c.row(tn);  // rows of the persistent buffers (ring, see Consts::t0)
+    // HZ: t + 1, the same for every running lane; `more` keeps a lane in its last cell out of the fetches (rows are plain: t0 = 0)
+    const int tn = HZ ? t + 1 : (t + 1 < T ? t + 1 : t);
+    [[maybe_unused]] const bool more = !HZ || t + 1 < T;
+    const int tr = (LEAN || HZ) ? t : c.row(t), tnr = (LEAN || HZ) ? tn : c.row(tn);  // rows of the persistent buffers (ring, see Consts::t0)
     const unsigned rb = opaque_uniform(rb0);  // see opaque_uniform(): no hoisting of e * rb
     // Large models: an index the compiler cannot see through (always 0) makes the big constant tables of the kernel
     // argument (sig_xi0: 45 doubles for the double cartpole, sig_eta: 21) scalar LOADS next to their single use in each
@@ -1023,12 +1037,23 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
       for (int e = 0; e < sym(D); ++e) wst(w, VOFF ? 0u : (D + e) * rb, VOFF ? voff[D + e] : bo, (ST_)S0[e]);
     }
 
+    if constexpr (HZ) {
+      if (more) {  // (no alpha_cell with horizons: refused by the resolver)
+        ff_cur = a.ff[tnr];
+        if (PREFETCH) {
+          const Window w = make_window(a.prior + (unsigned long)tnr * C::E_POST * B, (unsigned long)C::E_POST * rb);
+#pragma unroll
+          for (int e = 0; e < C::E_PRI; ++e) pri[e] = (R)wld<ST_>(w, VOFF ? 0u : (e) * rb, VOFF ? voff[e] : bo);
+        }
+      }
+    } else {
     ff_cur = a.ff[tnr];  // the next cell's flag, a whole cell ahead of its use
     if (!LEAN && a.alpha_cell) alpha_cur = a.alpha_cell[(long)tnr * B + b];
     if (PREFETCH) {  // pri is dead from here on: refill it with the next cell's rows
       const Window w = make_window(a.prior + (unsigned long)tnr * C::E_POST * B, (unsigned long)C::E_POST * rb);
 #pragma unroll
       for (int e = 0; e < C::E_PRI; ++e) pri[e] = (R)wld<ST_>(w, VOFF ? 0u : (e) * rb, VOFF ? voff[e] : bo);
+    }
     }
 
     // ---- 2. cost "observation": measurement update on z (i2c.py:390-407) --------------
@@ -1047,7 +1072,7 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
       for (int i = 0; i < sym(NZ); ++i) Sz[i] += alpha * (CONST_V ? xi0_v[i] : c.sig_xi0[i + kz]);
       cell_bad = flag_stage(cell_bad, kalman_update<D, NZ>(mu0, S0, mz, Sz, Sxz, zt), 2);
     }
-    if (!LEAN && PREFETCH && c.z_per_cell) {  // the target is consumed: fetch the next cell's
+    if (!LEAN && PREFETCH && c.z_per_cell && more) {  // the target is consumed: fetch the next cell's
 #pragma unroll
       for (int k = 0; k < NZ; ++k) zt[k] = a.z[((long)tnr * NZ + k) * B + b];
     }
@@ -1131,7 +1156,7 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
     sched_fence<(D >= 6)>();
 
     // ---- 4. terminal cost observation on the flagged cell, after J (i2c.py:430-443) ----
-    if (NZT > 0 && t == c.terminal_cell && c.has_Qf) {
+    if (NZT > 0 && (HZ ? (c.terminal_cell >= 0 && t == T - 1) : t == c.terminal_cell) && c.has_Qf) {
       constexpr int NT = C::NZT1;
       R mzt[NT], Szt[sym(NT)], Sxzt[NX * NT];
       if constexpr (REL::GAIN) {  // the helper solves this cell's J with the factor of sig_x3 as it is HERE (see ChunkReleaseGain)
@@ -1175,7 +1200,7 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
 // covariance control, its product with the tempered terminal prior (i2c.py:548-559).
 template <class M, typename R, int GRID = 0>
 I2C_FN void end_of_chain(const Consts<M, R>& c, R* temp, const int b, const R* m3f, const R* S3f, R* m3m, R* S3m,
-                         int32_t* status) {
+                         int32_t* status, const int t_last = -1) {  // t_last: the trajectory's own last cell (horizons); -1: T - 1
   constexpr int NX = M::NX;
   const bool wr = grid_writer<GRID>();
   if (c.has_x_terminal) {
@@ -1229,7 +1254,7 @@ I2C_FN void end_of_chain(const Consts<M, R>& c, R* temp, const int b, const R* m
 #pragma unroll
     for (int i = 0; i < NX; ++i) r1[i] += r2[i];
     symv<NX>(S3m, r1, m3m);
-    if (!ok && wr) set_status(status, b, 6, c.T - 1);
+    if (!ok && wr) set_status(status, b, 6, t_last >= 0 ? t_last : c.T - 1);
   } else {
 #pragma unroll
     for (int i = 0; i < NX; ++i) m3m[i] = m3f[i];
@@ -1295,7 +1320,7 @@ I2C_FN void gaussian_cost(const R* W, const bool w_diag, const R* mz, const R* S
 // Terminal observation statistics (i2c.py:567-570, 989-992): tr(Qf (errT errT^T + sig_z3_m)).
 template <class M, typename R, int GRID = 0>
 I2C_FN R terminal_obs_stats(const Consts<M, R>& c, const int b, const R* m3m, const R* S3m, R* term_stats,
-                            int32_t* status) {
+                            int32_t* status, const int t_last = -1) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NZT = C::NZT;
   const long B = c.B;
@@ -1306,7 +1331,7 @@ I2C_FN R terminal_obs_stats(const Consts<M, R>& c, const int b, const R* m3m, co
     R L3[sym(NX)], rinv3[NX], mzt[NT], Szt[sym(NT)];
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) L3[i] = S3m[i];
-    if (!chol<NX>(L3, rinv3) && wr) set_status(status, b, 6, c.T - 1);
+    if (!chol<NX>(L3, rinv3) && wr) set_status(status, b, 6, t_last >= 0 ? t_last : c.T - 1);
     transform<GRID, M, TermStruct<M>, NX, NT, false>(c.rule_x, m3m, S3m, L3, ObserveTermF<M, R>{params_of(c, b)}, mzt, Szt,
                                                   (R*)nullptr);
     R tv;
@@ -1583,8 +1608,15 @@ I2C_FN void reduce_partial(const Consts<M, R>& c, const R* cell_stats, const int
 // moves E_FWD + E_POST elements per cell instead of the two-pass form's ~2x that.
 // ------------------------------------------------------------------------------------------
 // LEANW: as in chunk_walk_body (no optional outputs, one shared target: a compile-time count of the memory operations of a cell).
-template <class M, typename R, int GRID = 0, typename S_ = R, bool LEANW = false>
-I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, S_>& a_in, const int b) {
+// HZ (per-trajectory horizons, see forward_sweep_body): the walk stays aligned in t across the wave -- the row offsets are wave-uniform
+// (make_window, wld, uniform_u32), which holds for a partly active wave but not for lanes that each start at their own Tb - 1. So the
+// lane first loads ITS row Tb - 1 with plain per-lane addressing, once per trajectory, and runs the end of the chain and the terminal
+// statistics on it; the time loop then comes down from T - 1 for the whole wave and the lane takes no part while t >= Tb. From its
+// first live cell on it is the walk as it was: the double-buffered form (d <= 5) finds that cell's row in `row` and fetches cell
+// t - 1, the d >= 6 form loads each cell at its top. Rows t >= Tb are neither read nor written.
+template <class M, typename R, int GRID = 0, typename S_ = R, bool LEANW = false, bool HZ = false>
+I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, S_>& a_in, const int b, [[maybe_unused]] const int Tb = 0) {
+  static_assert(!HZ || GRID == 0, "per-trajectory horizons: the one-lane walk");
   CellArgs<R, S_> a = a_in;
   if (LEANW) a.xm = nullptr, a.zpost = nullptr, a.cell_stats = nullptr;
   const bool z_per_cell = LEANW ? false : c.z_per_cell != 0;
@@ -1610,6 +1642,22 @@ I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, 
   const PolyTab<R>* const tab = VOFF ? &ptab : nullptr;
   R row[C::E_FWD], nxt[DOUBLE_BUFFER ? C::E_FWD : 1];
   R m3m[NX], S3m[sym(NX)];
+  if constexpr (HZ) {
+    const S_* in = a.fwd + ((unsigned long)(Tb - 1) * C::E_FWD) * B + b;  // the lane's own last row: per-lane addresses
+    if (DOUBLE_BUFFER) {
+#pragma unroll
+      for (int e = 0; e < C::E_FWD; ++e) row[e] = opaque((R)in[(unsigned long)e * B]);
+      end_of_chain<M, R, GRID>(c, a.temp, b, row + O_MU3, row + O_S3, m3m, S3m, a.status, Tb - 1);
+    } else {
+      R m3f[NX], S3f[sym(NX)];
+#pragma unroll
+      for (int e = 0; e < NX; ++e) m3f[e] = (R)in[(unsigned long)(O_MU3 + e) * B];
+#pragma unroll
+      for (int e = 0; e < sym(NX); ++e) S3f[e] = (R)in[(unsigned long)(O_S3 + e) * B];
+      end_of_chain<M, R, GRID>(c, a.temp, b, m3f, S3f, m3m, S3m, a.status, Tb - 1);
+    }
+    terminal_obs_stats<M, R, GRID>(c, b, m3m, S3m, a.term_stats, a.status, Tb - 1);
+  } else {
   {
     const Window w = make_window(a.fwd + (unsigned long)(T - 1) * C::E_FWD * B, (unsigned long)C::E_FWD * rb);
     if (DOUBLE_BUFFER) {
@@ -1633,9 +1681,13 @@ I2C_HD inline void backward_fused_body(const Consts<M, R>& c, const CellArgs<R, 
     }
   }
   terminal_obs_stats<M, R, GRID>(c, b, m3m, S3m, a.term_stats, a.status);
+  }
 
   R sum_m = R(0), sum_v = R(0);
   for (int t = T - 1; t >= 0; --t) {
+    if constexpr (HZ) {
+      if (t >= Tb) continue;  // the lane's chain has not begun
+    }
     if (DOUBLE_BUFFER) {
       const int tp = t > 0 ? t - 1 : 0;
       const Window w = make_window(a.fwd + (unsigned long)tp * C::E_FWD * B, (unsigned long)C::E_FWD * rb);
@@ -2130,10 +2182,10 @@ template <typename R> struct MstepArgs {
 // from term_stats; the prologue of k_forward_mstep (i2c_impl.hpp) has them in registers.
 template <class M, typename R>
 I2C_FN void mstep_update(const Consts<M, R>& c, const MstepArgs<R>& a, const int b, const R trT, const R stat, const R v, const R m,
-                         const R alpha) {
+                         const R alpha, const int T_own = 0) {  // T_own: the trajectory's own horizon (I2cProblem.horizons); 0: c.T
   using C = Consts<M, R>;
   const long B = c.B;
-  R tr = stat, sf = R(C::NZ) * R(c.T);
+  R tr = stat, sf = R(C::NZ) * R(T_own > 0 ? T_own : c.T);
   if (C::NZT > 0 && c.has_Qf) {
     tr += trT;
     sf += R(C::NZT);
@@ -2155,7 +2207,7 @@ I2C_FN void mstep_update(const Consts<M, R>& c, const MstepArgs<R>& a, const int
   a.stats_out[3 * B + b] = v;
 }
 template <class M, typename R>
-I2C_HD inline void mstep_body(const Consts<M, R>& c, const MstepArgs<R>& a, const int b) {
+I2C_HD inline void mstep_body(const Consts<M, R>& c, const MstepArgs<R>& a, const int b, const int T_own = 0) {
   using C = Consts<M, R>;
   const long B = c.B;
   // row 1 is the alpha statistic sum_t tr(QR (err err^T + sig_z0_m)); in the sigma-point path it IS the plan cost,
@@ -2163,7 +2215,7 @@ I2C_HD inline void mstep_body(const Consts<M, R>& c, const MstepArgs<R>& a, cons
   const R stat = a.term_stats[B + b], v = a.term_stats[2 * B + b];
   const R m = c.inference == I2C_INF_LINEARIZE ? a.term_stats[(long)(C::E_TERM - 1) * B + b] : stat;
   const R trT = (C::NZT > 0 && c.has_Qf) ? a.term_stats[b] : R(0);
-  mstep_update<M, R>(c, a, b, trT, stat, v, m, a.alpha[b]);
+  mstep_update<M, R>(c, a, b, trT, stat, v, m, a.alpha[b], T_own);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2182,12 +2234,14 @@ template <typename R> struct PropArgs {
   const uint8_t* expert;  // [T] ring or null: per-cell use_expert_controller (i2c.py:143,160); null: Consts::use_expert
 };
 
-template <class M, typename R, int GRID = 0>
-I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, const int b) {
+// HZ (per-trajectory horizons, see forward_sweep_body): the lane's cells end at its horizon Tb; every row address here is the lane's
+// own, so the one-cell-ahead fetches simply clamp to the lane's last cell, and the KL row is that of cell Tb - 1.
+template <class M, typename R, int GRID = 0, bool HZ = false>
+I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, const int b, [[maybe_unused]] const int Tb = 0) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NU = C::NU, NZ = C::NZ, D = C::D;
   const long B = c.B;
-  const int T = c.T;
+  const int T = HZ ? Tb : c.T;
   const bool wr = grid_writer<GRID>();  // (GRID_WAVE: lane 0 of the trajectory's wavefront; `true` otherwise)
   R mu_x[NX], sig_x[sym(NX)];
 #pragma unroll
@@ -2206,6 +2260,7 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
   // the arrival of the rows just requested -- is exposed EVERY cell (see forward_sweep_body). Fetched one cell ahead, and
   // everything settled before the loop (a load pending on the loop-entry path makes the waitcnt pass wait for vmcnt(0) at the top).
   unsigned ff_cur = a.ff[c.row(0)], ex_cur = a.expert ? (unsigned)a.expert[c.row(0)] : (unsigned)(c.use_expert != 0);
+  if constexpr (HZ) ff_cur = T == 1 ? 1u : ff_cur;  // (a trajectory of one cell stays in feed-forward mode: forward_sweep_body)
   ff_cur = opaque(ff_cur);
   ex_cur = opaque(ex_cur);
   if (PREFETCH) {
@@ -2237,7 +2292,12 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
   }
   R sum_m = R(0), sum_v = R(0);
 
-  for (int t = 0; t < T; ++t) {
+  // (HZ: the loop itself stays wave-uniform and a lane that is done sits the rest out -- leaving the loop lane by lane would keep a
+  //  copy of everything that is live behind it, the state and the sums, per exit: scratch for the d >= 6 models)
+  for (int t = 0; t < (HZ ? c.T : T); ++t) {
+    if constexpr (HZ) {
+      if (t >= T) continue;
+    }
     R nxt[PREFETCH ? C::E_PRI : 1];
     const int tn1 = t + 1 < T ? t + 1 : t;  // the next cell (flags), and where a second set of rows fits also its rows
     const int tn = PREFETCH ? tn1 : t;
@@ -2254,8 +2314,15 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
     const unsigned ff_now = ff_cur, ex_now = ex_cur;
     R zt_nxt[ZPRE ? NZ : 1];
     if (ZPRE) fetch_z(c.row(tn1), zt_nxt);
+    // (HZ: the flags are one [T] array for the whole batch: the next cell's index stays wave-uniform, clamped to the allocated T)
+    if constexpr (HZ) {
+      const int tnf = t + 1 < c.T ? t + 1 : t;
+      ff_cur = a.ff[tnf];
+      if (a.expert) ex_cur = a.expert[tnf];
+    } else {
     ff_cur = a.ff[c.row(tn1)];  // the next cell's flags, a whole cell ahead of their use
     if (a.expert) ex_cur = a.expert[c.row(tn1)];
+    }
     if (ff_now) {  // i2c.py:155-157: action marginal, but the joint still carries K sig_x (i2c.py:173-179)
 #pragma unroll
       for (int p = 0; p < NU; ++p)
@@ -2461,13 +2528,14 @@ template <typename R> struct RolloutArgs {
                      // 2: expert, hard weight (ExpertTimeIndexedLinearGaussianPolicy, linear.py:46-90)
 };
 
-template <class M, typename R>
-I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, const int n) {
+// HZ (per-trajectory horizons): rollout n runs trajectory n % B's horizon Tb; x_final and z_term are the state behind cell Tb - 1
+template <class M, typename R, bool HZ = false>
+I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, const int n, [[maybe_unused]] const int Tb = 0) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NU = C::NU, NZ = C::NZ, NZT = C::NZT, D = C::D, NA1 = M::NA > 0 ? M::NA : 1;
   const long B = c.B, N = (long)a.n_rollouts * B;
   const int b = n % c.B;
-  const int T = c.T;
+  const int T = HZ ? Tb : c.T;
   R pb[C::NP1];
   const R* prm = c.params;
   if constexpr (is_per_traj<M>::value) prm = param_ptr<M::NP>(params_of(c, b), pb);  // rollout n runs trajectory n % B's plant

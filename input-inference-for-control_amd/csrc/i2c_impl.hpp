@@ -209,6 +209,35 @@ I2C_KERNEL(LANE_BLOCK) k_plant_step(I2C_LANE_PARAMS const Consts<M, R> c, const 
   if (b < c.B) plant_step_body<M, R>(c, nz, a, (int)b);
 }
 
+// Per-trajectory horizons (I2cProblem.horizons, [B] int32): the HZ instantiations of the one-lane bodies (i2c_cell.hpp), fp64,
+// sigma-point rule. Lane b reads its horizon once, clamped to [1, T], and hands it to the body; rollout n takes column n % B.
+// One variant per sweep -- the generic forward cell, the walk with every optional output -- so a model adds five kernels.
+template <class M, typename R>
+I2C_KERNEL(LANE_BLOCK) k_forward_hz(I2C_LANE_PARAMS const Consts<M, R> c, const FwdArgs<R, R> a, const int32_t* const hz) {
+  const long b = I2C_LANE_X(LANE_BLOCK);
+  if (b < c.B) forward_sweep_body<M, R, false, 0, R, NoRelease, true>(c, a, (int)b, NoRelease{0}, clamp_horizon(hz[b], c.T));
+}
+template <class M, typename R>
+I2C_KERNEL(LANE_BLOCK) k_bwd_fused_hz(I2C_LANE_PARAMS const Consts<M, R> c, const CellArgs<R, R> a, const int32_t* const hz) {
+  const long b = I2C_LANE_X(LANE_BLOCK);
+  if (b < c.B) backward_fused_body<M, R, 0, R, false, true>(c, a, (int)b, clamp_horizon(hz[b], c.T));
+}
+template <class M, typename R>
+I2C_KERNEL(LANE_BLOCK) k_mstep_hz(I2C_LANE_PARAMS const Consts<M, R> c, const MstepArgs<R> a, const int32_t* const hz) {
+  const long b = I2C_LANE_X(LANE_BLOCK);
+  if (b < c.B) mstep_body<M, R>(c, a, (int)b, clamp_horizon(hz[b], c.T));
+}
+template <class M, typename R>
+I2C_KERNEL(LANE_BLOCK) k_propagate_hz(I2C_LANE_PARAMS const Consts<M, R> c, const PropArgs<R> a, const int32_t* const hz) {
+  const long b = I2C_LANE_X(LANE_BLOCK);
+  if (b < c.B) propagate_body<M, R, 0, true>(c, a, (int)b, clamp_horizon(hz[b], c.T));
+}
+template <class M, typename R>
+I2C_KERNEL(LANE_BLOCK) k_rollout_hz(I2C_LANE_PARAMS const Consts<M, R> c, const RolloutArgs<R> a, const int32_t* const hz) {
+  const long n = I2C_LANE_X(LANE_BLOCK);
+  if (n < (long)a.n_rollouts * c.B) rollout_body<M, R, true>(c, a, (int)n, clamp_horizon(hz[n % c.B], c.T));
+}
+
 // Sum of the per-cell cost statistics over t: REDUCE_PARTS lanes per trajectory, fixed summation order; with `ms.alpha`
 // set (i2c_learn) the temperature M-step rides on it. The device form exchanges the partial sums through LDS; the host
 // form walks the same partition in the same order.
@@ -1339,6 +1368,22 @@ template <class M, typename R, typename S = R> struct Impl {
     return by_default(req) && p->B <= (knob > -2 ? knob : quad_chunk_stitch_max_b<M>::value) && quad_passes_supported(p, unit);
   }
 
+  // Per-trajectory horizons (I2cProblem.horizons): the HZ kernels exist for the one-lane bodies in fp64 under the sigma-point rule, for
+  // models without process_noise; the forward, backward and propagate sweeps then resolve to I2C_FAMILY_LANE (group_lanes 0 and -1
+  // alike: no default hands a sweep to another family) and the backward sweep to the fused walk, whatever schedule is asked for. What
+  // those kernels do not cover is refused here, before any launch: I2C_ENOTSUP for what is not compiled, I2C_EINVAL for a problem whose
+  // fields contradict a horizon per trajectory (a moved ring, per-cell temperatures -- both belong to the MPC loop --, a terminal cell
+  // that is not "each trajectory's last one", T - 1, or none).
+  static constexpr bool HAS_HORIZONS = LANE && sizeof(R) == 8 && !MIXED && !NOISE;
+  static int horizons_supported(const I2cProblem* p) {
+    if (!HAS_HORIZONS) return I2C_ENOTSUP;
+    if (p->group_lanes != 0 && p->group_lanes != -1) return I2C_ENOTSUP;
+    if (p->inference != I2C_INF_CUBATURE) return I2C_ENOTSUP;
+    if (p->t0 != 0 || p->alpha_cell) return I2C_EINVAL;
+    if (p->terminal_cell != p->T - 1 && p->terminal_cell != -1) return I2C_EINVAL;
+    return I2C_OK;
+  }
+
   // THE place that decides which kernel family and which backward schedule serve a problem (i2c_kernel_family() and
   // i2c_backward_schedule() report it; every entry point below dispatches from it)
   static Plan resolve(const I2cProblem* p) {
@@ -1347,6 +1392,16 @@ template <class M, typename R, typename S = R> struct Impl {
     const Request req = request(p->group_lanes, p->inference);
     Plan pl;
     pl.rule = p->inference;
+    if (p->horizons) {  // per-trajectory horizons: the one-lane kernels and the fused walk, or the refusal (horizons_supported)
+      const int rc = horizons_supported(p);
+      pl.forward = pl.backward = pl.propagate = rc == I2C_OK ? I2C_FAMILY_LANE : rc;
+      pl.filter = filter_family(p, req == REQ_GRID ? request(p->group_lanes, I2C_INF_CUBATURE) : req);  // (reads no horizon)
+      pl.schedule = rc == I2C_OK ? I2C_BWD_FUSED : rc;
+      pl.walker = I2C_ENOTSUP;
+      pl.compose = pl.stitch = rc == I2C_OK ? I2C_ENOTSUP : rc;
+      pl.fwd_tm = pl.fusable = false;
+      return pl;
+    }
     if constexpr (NOISE) {
       if (p->inference != I2C_INF_CUBATURE) {
         pl.forward = pl.backward = pl.propagate = pl.filter = pl.schedule = pl.walker = pl.compose = pl.stitch = I2C_ENOTSUP;
@@ -1474,6 +1529,10 @@ template <class M, typename R, typename S = R> struct Impl {
     if (pl.forward < 0) return pl.forward;
     const FwdArgs<R, S> a{(const S*)prior, (S*)fwd, (S*)prior_out, (const R*)p->x0, (const R*)p->sig_x0,
                           (const R*)p->z,  (const R*)p->alpha, (const R*)p->alpha_cell, p->feedforward, status, p->expert};
+    if (p->horizons) {  // (resolved to the one-lane kernels: horizons_supported)
+      if constexpr (HAS_HORIZONS) return launch(k_forward_hz<M, R>, p->B, 1, LANE_BLOCK, stream, c, a, p->horizons);
+      return I2C_ENOTSUP;
+    }
     if (pl.forward == I2C_FAMILY_WAVE) {
       if constexpr (HAS_WAVE) return launch_wave<WK_FORWARD, M, R, S>(c, a, stream);
     }
@@ -1528,6 +1587,10 @@ template <class M, typename R, typename S = R> struct Impl {
                            (R*)cell_stats, (R*)term_stats, (R*)p->temp,    status,   terminal_alpha(p, c)};
     const int mode = L.schedule;
     int rc = I2C_ENOTSUP;
+    if (p->horizons) {  // one schedule: the fused walk, each lane from its own last cell
+      if constexpr (HAS_HORIZONS) return launch(k_bwd_fused_hz<M, R>, p->B, 1, LANE_BLOCK, stream, c, a, p->horizons);
+      return I2C_ENOTSUP;
+    }
     if (pl.backward == I2C_FAMILY_WAVE) {
       // the fused walk; two-pass (scan, one wave per cell, reduction -- with the M-step riding on it in i2c_learn) when that schedule
       // is asked for and its workspaces exist
@@ -1653,6 +1716,7 @@ template <class M, typename R, typename S = R> struct Impl {
   static int riccati(const I2cProblem* p, const void* prior_out, const void* fwd, const void* xm, void* post, void* ric,
                      int32_t* status, void* stream) {
     if constexpr (MIXED || NOISE) return I2C_ENOTSUP;  // (NOISE: the Riccati messages read the constant sig_eta alone)
+    if (p->horizons) return I2C_EINVAL;  // (a Linearize pass: no per-trajectory horizons)
     if constexpr (LANE) {
       if (!lane_request(p->group_lanes)) return I2C_ENOTSUP;
       const C c = make_consts<M, R>(p, 0.0, 0);
@@ -1665,6 +1729,10 @@ template <class M, typename R, typename S = R> struct Impl {
 
   // `c`: the constants of the call with the M-step's tolerance
   static int run_mstep(const I2cProblem* p, const C& c, const MstepArgs<R>& a, void* stream) {
+    if (p->horizons) {  // sf = nz T_b (+ nzt)
+      if constexpr (HAS_HORIZONS) return horizons_supported(p) != I2C_OK ? horizons_supported(p) : launch(k_mstep_hz<M, R>, p->B, 1, LANE_BLOCK, stream, c, a, p->horizons);
+      return I2C_ENOTSUP;
+    }
     return launch(k_mstep<M, R>, p->B, 1, LANE_BLOCK, stream, c, a);
   }
   static int mstep(const I2cProblem* p, const void* term_stats, double tol, int update, void* stats_out, void* stream) {
@@ -1789,6 +1857,7 @@ template <class M, typename R, typename S = R> struct Impl {
   // (the caller then advances I2cProblem.t0 by one and moves terminal_cell).
   static int mpc_step(const I2cProblem* p, const I2cMpcStep* m, void* stream) {
     if constexpr (MIXED) return I2C_ENOTSUP;
+    if (p->horizons) return I2C_EINVAL;  // the ring of the MPC loop has one horizon
     const Plan pl = resolve(p);
     const C cf = forward_consts(p), cb = make_consts<M, R>(p, 0.0, 0);
     const Launches L = launches(p, pl, cb, m->xm, m->zpost, m->cell_stats, false);
@@ -1806,6 +1875,7 @@ template <class M, typename R, typename S = R> struct Impl {
   static int shift(const I2cProblem* p, void* post, const void* cell_init, const void* alpha_init, const void* z_new, void* action,
                    void* stream) {
     if constexpr (MIXED) return I2C_ENOTSUP;
+    if (p->horizons) return I2C_EINVAL;
     return run_shift(p, make_consts<M, R>(p, 0.0, 0), post, cell_init, alpha_init, z_new, action, stream);
   }
   static int run_shift(const I2cProblem* p, const C& c, void* post, const void* cell_init, const void* alpha_init, const void* z_new,
@@ -1827,8 +1897,13 @@ template <class M, typename R, typename S = R> struct Impl {
                      void* stream) {
     if constexpr (MIXED) return I2C_ENOTSUP;
     const C c = make_consts<M, R>(p, 0.0, 0);
+    if (p->horizons && horizons_supported(p) != I2C_OK) return horizons_supported(p);
     RolloutArgs<R> a{(const R*)post, (const R*)p->x0, (const R*)p->sig_x0, (const R*)eps_x0, (const R*)eps_x,
                      (const R*)eps_u, (R*)xu, (R*)z, (R*)x_final, (R*)z_term, n_rollouts, policy};
+    if (p->horizons) {  // rollout n ends behind cell T_b - 1 of trajectory b = n % B
+      if constexpr (HAS_HORIZONS) return launch(k_rollout_hz<M, R>, (long)n_rollouts * p->B, 1, LANE_BLOCK, stream, c, a, p->horizons);
+      return I2C_ENOTSUP;
+    }
     return launch(k_rollout<M, R>, (long)n_rollouts * p->B, 1, LANE_BLOCK, stream, c, a);
   }
 
@@ -1852,6 +1927,10 @@ template <class M, typename R, typename S = R> struct Impl {
     if (pl.propagate < 0) return pl.propagate;
     PropArgs<R> a{(const R*)post, (R*)prop, (R*)prop_stats, (const R*)p->x0, (const R*)p->sig_x0,
                   (const R*)p->z, p->feedforward, status, p->expert};
+    if (p->horizons) {
+      if constexpr (HAS_HORIZONS) return launch(k_propagate_hz<M, R>, p->B, 1, LANE_BLOCK, stream, c, a, p->horizons);
+      return I2C_ENOTSUP;
+    }
     if (pl.propagate == I2C_FAMILY_QUAD) {
       if constexpr (HAS_QUAD_PROP) return launch_quad_propagate<M, R>(c, a, stream);
     }

@@ -22,6 +22,16 @@ def shard_sizes(total, world):
     return [hi - lo for lo, hi in (shard_range(total, r, world) for r in range(world))]
 
 
+def shard_rows(a, rank, world):
+    """This rank's slice of a per-trajectory input whose first axis is the global batch -- x0, mu_u, model_params, and the
+    per-trajectory `horizons` of BatchedI2c alike: a sharded engine is built from shard_rows(...) of each of them (`horizon`, the
+    allocated number of cells, stays the global one, so the gathered controllers of all ranks have the same shape). None stays None."""
+    if a is None:
+        return None
+    lo, hi = shard_range(len(a), rank, world)
+    return a[lo:hi]
+
+
 def _all_gather_rows(t, total=None, group=None):
     """All-gather along dim 0 in ONE collective. `total` = the global number of rows: the shards are the contiguous partition of
     shard_range, so every rank computes every shard size itself and no size exchange is needed. With more than one rank `total`

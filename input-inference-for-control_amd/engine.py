@@ -57,7 +57,7 @@ class BatchedI2c:
                  z_traj=None, batch=None, dtype=torch.float64, device=None, lib=None, dtemp=1.0,
                  keep_zpost=True, keep_prior=False, keep_xm=True, backward_mode="auto", inference="cubature",
                  gh_degree=None, group_lanes=0, storage_dtype=None, allow_inexact=False, keep_prior_joint=False, post_layout=None,
-                 deterministic_family=False, overlap_propagation=True, model_params=None):
+                 deterministic_family=False, overlap_propagation=True, model_params=None, horizons=None):
         self.lib = lib if lib is not None else _native.load_library()
         if device is None:
             device = "cpu" if self.lib.is_host_sim else "cuda"
@@ -215,6 +215,11 @@ class BatchedI2c:
             if self.group_lanes not in (0, -1) + ((64, _native.LANES_QUAD) if quad_ok else ()):
                 raise ValueError(f"group_lanes={self.group_lanes}: a model with process_noise runs on the one-lane kernels (0 or -1)"
                                  + (f" or the quad kernels (64 or {_native.LANES_QUAD})" if quad_ok else ""))
+        # Per-trajectory horizons (I2cProblem.horizons): trajectory b consists of cells 0 .. horizons[b] - 1; `horizon` stays the
+        # allocated number of rows T >= max(horizons). Served by the one-lane kernels in fp64 under the sigma-point rule with the fused
+        # backward walk (include/i2c_hip.h); checked here, on the host, before anything is allocated.
+        self._horizons = None
+        self._horizons_np = None if horizons is None else self._check_horizons(horizons, inference)
         self.linearize = inference == "linearize"
         self.gauss_hermite = inference == "gauss_hermite"
         self.gh_degree = 0
@@ -327,6 +332,8 @@ class BatchedI2c:
         self._params_b = None
         if model_params is not None:
             self._params_b = self._params_to_device(model_params)
+        if self._horizons_np is not None:
+            self._horizons = torch.as_tensor(self._horizons_np, dtype=torch.int32, device=dev)
         self._problem = self._make_problem()
         mode = self.lib.i2c_backward_schedule(C.byref(self._problem))
         if mode not in (_native.BWD_TWO_PASS, _native.BWD_FUSED, _native.BWD_CHUNKED):
@@ -408,7 +415,77 @@ class BatchedI2c:
         p.feedforward = self.feedforward.data_ptr()
         p.expert = self.expert_cells.data_ptr() if self.expert_cells is not None else None
         p.model_params_b = self._params_b.data_ptr() if self._params_b is not None else None
+        p.horizons = self._horizons.data_ptr() if self._horizons is not None else None
         return p
+
+    def _check_horizons(self, horizons, inference=None):
+        """A sequence of B ints in [1, T] -> int32 array; ValueError for a wrong length or value, and for every combination the
+        kernels with per-trajectory horizons do not serve (the message names what to drop)."""
+        h = horizons.detach().cpu().numpy() if torch.is_tensor(horizons) else np.asarray(horizons)
+        if h.ndim != 1 or h.shape[0] != self.B:
+            raise ValueError(f"horizons must be a sequence of B = {self.B} ints, got shape {h.shape}")
+        if not np.issubdtype(h.dtype, np.integer):
+            if not np.all(np.isfinite(h)) or np.any(h != np.round(h)):
+                raise ValueError("horizons must be integers")
+        h = h.astype(np.int64)
+        if np.any(h < 1) or np.any(h > self.H):
+            raise ValueError(f"horizons must lie in [1, horizon] = [1, {self.H}] (`horizon` is the allocated number of cells and "
+                             f"must be at least max(horizons)), got min {int(h.min())}, max {int(h.max())}")
+        inference = self.inference if inference is None else inference
+        drop = []
+        if self.dims.group_only:
+            raise ValueError(f"horizons: {type(self.sys).__name__} has no one-lane kernels (nx + nu > 8); drop horizons and solve "
+                             "each horizon in an engine of its own")
+        if self.group_lanes not in (0, -1):
+            drop.append(f"group_lanes={self.group_lanes} (per-trajectory horizons run on the one-lane kernels: 0 or -1)")
+        if inference != "cubature":
+            drop.append(f"inference={inference!r} (the sigma-point rule \"cubature\" only)")
+        if self.dtype != torch.float64 or self.mixed:
+            drop.append("dtype / storage_dtype float32 (fp64 arithmetic and storage only)")
+        if self.has_process_noise:
+            drop.append("the model's process_noise member (constant process noise only)")
+        if getattr(self, "alpha_cell", None) is not None:
+            drop.append("per-cell temperatures (enable_per_cell_alpha)")
+        if getattr(self, "t0", 0) != 0 or getattr(self, "terminal_cell", self.H - 1) not in (self.H - 1, -1):
+            drop.append("the moved horizon ring of the MPC loop (shift_horizon / mpc_step)")
+        if drop:
+            raise ValueError("horizons cannot be combined with " + "; ".join(drop) + ": drop that, or drop horizons")
+        return h.astype(np.int32)
+
+    @property
+    def horizons(self):
+        """Per-trajectory horizons as a (B,) int32 tensor, or None when every trajectory has the allocated horizon."""
+        return None if self._horizons is None else self._horizons.clone()
+
+    def set_horizons(self, h):
+        """Replace the per-trajectory horizons (a sequence of B ints in [1, horizon]) in place; an engine built without them gets
+        its buffer here and from then on runs the one-lane kernels with the fused backward walk. Rows beyond a trajectory's new
+        horizon keep whatever they held."""
+        v = torch.as_tensor(self._check_horizons(h), dtype=torch.int32, device=self.device)
+        self._horizons_np = v.cpu().numpy()
+        if self._horizons is None:
+            self._horizons = v
+            self.refresh_problem()
+            mode = self.lib.i2c_backward_schedule(C.byref(self._problem))
+            self._check(0 if mode == _native.BWD_FUSED else (mode if mode < 0 else -1), "i2c_backward_schedule")
+            self.fused_backward, self.backward_schedule = True, "fused"
+        else:
+            self._horizons.copy_(v)
+
+    def valid_cells(self):
+        """(B, T) bool mask of the cells that exist: cell t of trajectory b with t < horizons[b] (all of them without horizons)."""
+        t = torch.arange(self.H, device=self.device)
+        if self._horizons is None:
+            return torch.ones(self.B, self.H, dtype=torch.bool, device=self.device)
+        return t[None, :] < self._horizons[:, None].to(t.dtype)
+
+    def _cells_per_trajectory(self):
+        """T_b as a (B,) tensor in the arithmetic dtype, or the float T without horizons."""
+        return float(self.H) if self._horizons is None else self._horizons.to(self.dtype)
+
+    def _no_horizons(self, what):
+        if self._horizons is not None:
+            raise ValueError(f"{what} is not available with per-trajectory horizons: drop horizons")
 
     def _params_to_device(self, params):
         """(B, NP) array / tensor of per-trajectory model parameters -> a new [NP][B] device tensor in the arithmetic dtype."""
@@ -510,6 +587,7 @@ class BatchedI2c:
         """I2cGraph._backward_ricatti_msgs (i2c.py:888-893): Riccati-form backward messages after a Linearize
         forward/backward pass. Overwrites K, k, sigK with the Riccati-form controller (as the reference does) and
         returns the backward state message in information form, (nu_x0_b (B, T, nx), lambda_x0_b (B, T, nx, nx))."""
+        self._no_horizons("riccati_sweep()")
         if not self.linearize:
             raise RuntimeError("the Riccati messages belong to the Linearize() path (i2c.py:612-678)")
         if self.prior_out is None or self.xm is None:
@@ -561,7 +639,7 @@ class BatchedI2c:
 
     def _alpha_from_propagation(self):
         """calculate_alpha(sum of propagated observation covariances) (i2c.py:901-904, 934-939)."""
-        return self.prop_stats[0] / float(self.nz * self.H)
+        return self.prop_stats[0] / (self.nz * self._cells_per_trajectory())
 
     def alpha_mstep(self, update_alpha=True):
         """compute_update_alpha (i2c.py:921-963) alone: alpha_hat from the backward sweep's statistics, the clamp, and --
@@ -607,7 +685,7 @@ class BatchedI2c:
             ps = self.prop_stats.clone()  # ONE copy per iteration (cost mean, cost variance, terminal KL): the rows below are views
             self.costs_pf.append(ps[0])
             self.costs_pf_var.append(ps[1])
-            self.alphas_pf.append(ps[0] / float(self.nz * self.H))  # = _alpha_from_propagation()
+            self.alphas_pf.append(ps[0] / (self.nz * self._cells_per_trajectory()))  # = _alpha_from_propagation()
         else:
             if getattr(self, "_minus_one", None) is None:
                 self._minus_one = torch.full_like(out[2], -1.0)  # (one constant row shared by every entry: no fill kernel per iteration)
@@ -681,7 +759,7 @@ class BatchedI2c:
         self.em_iter += n_iters
         self.stats_out.copy_(hist[-1])
         self.prop_stats.copy_(histp[-1])
-        apf = histp[:, 0] / float(self.nz * self.H)  # = _alpha_from_propagation() of every iteration
+        apf = histp[:, 0] / (self.nz * self._cells_per_trajectory())  # = _alpha_from_propagation() of every iteration
         for it in range(n_iters):
             self.costs_m.append(hist[it, 2])
             self.costs_m_var.append(hist[it, 3])
@@ -733,6 +811,7 @@ class BatchedI2c:
         (the temperature at policy construction), because update_xi (i2c.py:976-981) only reaches the cells
         in the list when alpha changes and alpha is frozen inside the loop. Reproduced with a [T][B]
         per-cell temperature that follows the cells through the shift."""
+        self._no_horizons("enable_per_cell_alpha()")
         if self.alpha_cell is None:
             self.alpha_init = self.alpha.clone()
             self.alpha_cell = self.alpha.reshape(1, -1).repeat(self.H, 1).contiguous()
@@ -765,6 +844,7 @@ class BatchedI2c:
         row of the dropped one (i2c_shift_horizon) and the ring offset advances -- nothing else moves. The `terminal_cell`
         flag stays with the cell it was set on (i2c.py:822), so its index decreases. Returns the dropped cell's action
         moments (mu_u (B, nu), sig_u packed (B, sym nu)) if want_action."""
+        self._no_horizons("shift_horizon()")
         assert self.prior is self.post, "shift_horizon() between a sweep and its update_priors()"
         if want_action and getattr(self, "_mpc_action", None) is None:
             self._mpc_action = torch.empty(self.nu + sym_size(self.nu), self.B, dtype=self.dtype, device=self.device)
@@ -784,6 +864,7 @@ class BatchedI2c:
         buffers are a ring). Returns (mu_u (B, nu), sig_u packed (B, sym nu)) device tensors: the first planned action BEFORE
         the shift (cells[0].mu_u0_m, sig_u0_m). Same numbers as ckf_filter + n_iter x (forward_backward, update_priors) +
         shift_horizon."""
+        self._no_horizons("mpc_step()")
         assert self.prior is self.post, "mpc_step() between a sweep and its update_priors()"
         st = _native.I2cMpcStep()
         st.do_filter = int(y is not None)
@@ -897,6 +978,7 @@ class BatchedI2c:
         does not, where the reference's loop clips first and records / prices the clipped action (mpc_quad.py:645-647, 659). They
         agree whenever the plan respects the limits.
         A trajectory that fails numerically is flagged in status (failures()); its rows go non-finite, the others are untouched."""
+        self._no_horizons("run_closed_loop()")
         assert self.prior is self.post, "run_closed_loop() between a sweep and its update_priors()"
         N, B, T, dev, dt = int(n_steps), self.B, self.H, self.device, self.dtype
         nx, nu, nz, ny = self.nx, self.nu, self.nz, self.dims.ny
@@ -1010,8 +1092,12 @@ class BatchedI2c:
             sig1 = unpack_sym(self.sig_x0.T.to(torch.float64), nx)
         else:
             o = self.d + sym_size(self.d)
-            mu1 = self.prop[-1, o: o + nx, :].T.to(torch.float64)
-            sig1 = unpack_sym(self.prop[-1, o + nx: o + nx + sym_size(nx), :].T.to(torch.float64), nx)
+            if self._horizons is None:
+                last = self.prop[-1]
+            else:  # each trajectory's own last cell
+                last = self.prop[self._horizons.long() - 1, :, torch.arange(self.B, device=self.device)].T
+            mu1 = last[o: o + nx, :].T.to(torch.float64)
+            sig1 = unpack_sym(last[o + nx: o + nx + sym_size(nx), :].T.to(torch.float64), nx)
         mu2 = torch.as_tensor(self.mu_x_terminal, dtype=torch.float64, device=self.device)
         sig2 = torch.as_tensor(self.sig_x_terminal, dtype=torch.float64, device=self.device)
         diff = mu2 - mu1
