@@ -523,6 +523,68 @@ int i2c_rollout(const I2cProblem* p, const void* post, int n_rollouts, int polic
                 void* stream);
 
 /*
+ * Monte-Carlo policy evaluation on the device: n_rollouts simulations of every trajectory's controller through the noisy plant,
+ * reduced to the cost of every rollout, its statistics per trajectory, and the mean and covariance of (x_t, u_t) over the rollouts
+ * (the reference does this on the host after every iteration: env.batch_eval feeding StochasticTrajectoryEvaluator,
+ * i2c/utils.py:150-265). No noise comes in and no trajectory goes out: the draws are made in the kernel, the sums stay in fp64.
+ *
+ * Rollout (r, b) is exactly what i2c_rollout simulates for n = r * B + b: same policies, same plant (p->model_params or column b of
+ * p->model_params_b), the ring (p->t0), the trajectory-major post of a wave-capable model, per-trajectory horizons (trajectory b
+ * runs T_b cells; rows t >= T_b of xu_mean / xu_cov are never written), and a model with process_noise leaves a rollout NaN from
+ * the step whose covariance is not positive definite.
+ *
+ * Cost of a rollout: the problem's own quadratic cost
+ *     sum_{t < T_b} (z_t - zg_t)^T QR (z_t - zg_t),  z_t = observe(x_t, u_t),  zg_t = row t of p->z (z_per_cell) or p->zg,
+ *   plus, with has_Qf, (z_T - zg_term)^T Qf (z_T - zg_term), z_T = observe_terminal of the state behind the last cell. This is
+ *   quadratic_trajectory_cost of i2c/utils.py; the reference's StochasticTrajectoryEvaluator differs from it (it leaves out the last
+ *   running step and prices only the first dim_x terminal features).
+ * Moments: of (x_t, u_t) over the R rollouts of a trajectory, summed as differences delta from the planned mean (the head of the
+ *   post row): S1 = sum delta, S2 = sum delta delta^T, mean = mu + S1 / R, cov = (S2 - S1 S1^T / R) / (R - 1) (R = 1: NaN).
+ *   Lane (part q, trajectory b) runs rollouts q, q + parts, ... and keeps its sums in work [parts][T][d + SYM(d)][B]; the first
+ *   rollout of a lane stores, later ones add, so the workspace needs no clearing; a second launch adds the parts in ascending
+ *   order. No atomics anywhere: the same call gives the same bits. parts = 0: min(R, max(1, ceil(65536 / B))).
+ * A trajectory with a rollout whose cost is not finite gets NaN in its four cost_stats rows and the count in n_bad; its cost row
+ *   and its moments before the first non-finite step stay what they are, every other trajectory is untouched by it.
+ *
+ * The generator: Philox4x32-10 (Salmon et al., SC'11: multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85,
+ * ten rounds), one call per PAIR of standard normals of one rollout step (csrc/i2c_random.hpp):
+ *     key     = (seed & 0xffffffff, seed >> 32)
+ *     counter = (first_trajectory + b,  r,  t,  kind + 4 * j)    kind: 0 x0 (t = 0xffffffff), 1 process noise, 2 action noise
+ *     a = (w0 << 21) | (w1 >> 11);  u1 = (a + 1) * 2^-53  in (0, 1]
+ *     b = (w2 << 21) | (w3 >> 11);  u2 = b * 2^-53        in [0, 1)
+ *     rho = sqrt(-2 log(u1));  normal 2j = rho cos(2 pi u2),  normal 2j + 1 = rho sin(2 pi u2)   (an odd last normal is dropped)
+ *   A draw depends on (seed, global trajectory, r, t, kind) and on nothing else -- not on B, parts or the launch shape: a shard
+ *   that passes the global index of its first trajectory reproduces the single-process run, and one seed on two calls gives
+ *   common random numbers.
+ *
+ * I2C_EINVAL: NULL cost or post, n_rollouts < 1, a policy outside 0..2, xu_cov without xu_mean, xu_mean without work, parts < 0 or
+ *   parts > n_rollouts, first_trajectory + B beyond 32 bits. I2C_ENOTSUP: I2C_F32 and I2C_F64_F32S (the sums are fp64), and a model
+ *   library built before this entry point existed (no i2c_model_ops_size symbol; tables handed straight to i2c_register_model
+ *   count as such). All before any launch.
+ */
+typedef struct I2cRolloutEval {
+  int32_t n_rollouts;        /* R >= 1 per trajectory */
+  int32_t policy;            /* as i2c_rollout: 0 linear, 1 expert soft, 2 expert hard */
+  int32_t noise;             /* bits: 1 process noise, 2 action noise (chol(sigK)), 4 x0 ~ N(x0, sig_x0) */
+  int32_t parts;             /* lanes per trajectory for the moment sums; 0 = the library's rule */
+  uint64_t seed;             /* key of the generator */
+  uint32_t first_trajectory; /* global index of this problem's trajectory 0 (a shard passes the start of its range) */
+  uint32_t reserved0;
+  const void *eps_x0, *eps_x, *eps_u; /* optional GIVEN standard normals, layouts of i2c_rollout (n = r * B + b): a non-NULL
+                                         pointer switches that kind on and replaces the generator for it */
+  void* cost;        /* [R][B]  required: cost of rollout n */
+  void* cost_stats;  /* [4][B]  or NULL: mean, unbiased variance, min, max over the R rollouts */
+  int32_t* n_bad;    /* [B]     or NULL: rollouts whose cost is not finite */
+  void* xu_mean;     /* [T][d][B]      or NULL */
+  void* xu_cov;      /* [T][SYM(d)][B] or NULL (packed lower, row-major, as everywhere); needs xu_mean */
+  void* work;        /* workspace of the size the call below reports; may be NULL when xu_mean is NULL */
+} I2cRolloutEval;
+/* Bytes of I2cRolloutEval.work for the moments of this problem, parts * T * (d + SYM(d)) * B * 8, with `parts` resolved as the call
+ * itself resolves it and reported in *parts_out (optional). Reads scalar fields only; 0 for a problem or request the call refuses. */
+size_t i2c_rollout_eval_workspace(const I2cProblem* p, const I2cRolloutEval* ev, int32_t* parts_out);
+int i2c_rollout_eval(const I2cProblem* p, const void* post, const I2cRolloutEval* ev, void* stream);
+
+/*
  * One cubature-Kalman-filter step of the MPC state estimator: replaces
  * PartiallyObservedMpcPolicy.filter (i2c/policy/mpc.py:125-145; duplicate in
  * scripts/mpc_state_est/mpc_quad.py:135-155): predict the belief N(mu, cov) through sys.forward

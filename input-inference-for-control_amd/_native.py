@@ -127,6 +127,18 @@ class I2cEpisode(C.Structure):
     ]
 
 
+class I2cRolloutEval(C.Structure):
+    _fields_ = [
+        ("n_rollouts", C.c_int32), ("policy", C.c_int32), ("noise", C.c_int32), ("parts", C.c_int32),
+        ("seed", C.c_uint64), ("first_trajectory", C.c_uint32), ("reserved0", C.c_uint32),
+        ("eps_x0", C.c_void_p), ("eps_x", C.c_void_p), ("eps_u", C.c_void_p),
+        ("cost", C.c_void_p), ("cost_stats", C.c_void_p), ("n_bad", C.c_void_p),
+        ("xu_mean", C.c_void_p), ("xu_cov", C.c_void_p), ("work", C.c_void_p),
+    ]
+
+
+NOISE_PROCESS, NOISE_ACTION, NOISE_X0 = 1, 2, 4  # I2cRolloutEval.noise
+
 _SIGNATURES = {
     "i2c_abi_version": (C.c_int, []),
     "i2c_problem_size": (C.c_size_t, []),
@@ -155,6 +167,8 @@ _SIGNATURES = {
     "i2c_mpc_step": (C.c_int, [C.POINTER(I2cProblem), C.POINTER(I2cMpcStep), C.c_void_p]),
     "i2c_shift_horizon": (C.c_int, [C.POINTER(I2cProblem)] + [C.c_void_p] * 6),
     "i2c_rollout": (C.c_int, [C.POINTER(I2cProblem), C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "i2c_rollout_eval_workspace": (C.c_size_t, [C.POINTER(I2cProblem), C.POINTER(I2cRolloutEval), C.POINTER(C.c_int32)]),
+    "i2c_rollout_eval": (C.c_int, [C.POINTER(I2cProblem), C.c_void_p, C.POINTER(I2cRolloutEval), C.c_void_p]),
     "i2c_ckf_filter": (
         C.c_int,
         [C.POINTER(I2cProblem), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],

@@ -90,11 +90,12 @@ def model_lib_path(name, host_sim=False, out_dir=None):
     return os.path.join(out_dir or LIB_DIR, f"libi2c_model_{name}{'_hostsim' if host_sim else ''}.so")
 
 
-def build_model(header, struct=None, name=None, host_sim=False, out_dir=None, force=False, verbose=True):
+def build_model(header, struct=None, name=None, host_sim=False, out_dir=None, force=False, verbose=True, entry_defs=()):
     """Compile ONE out-of-tree model header into a model library: csrc/i2c_model_tu.hip once per precision with the header
     included (-DI2C_TU_HEADER) plus csrc/i2c_model_entry.hip (the C symbols i2c_load_model resolves). `struct` = the functor's
     name in namespace i2c (default: the header's file name in CamelCase), `name` = the library's name (default: the file name).
-    host_sim=True builds the CPU simulation of the same kernels with g++ (tests only)."""
+    host_sim=True builds the CPU simulation of the same kernels with g++ (tests only). entry_defs: extra -D flags for
+    csrc/i2c_model_entry.hip alone (tests: -DI2C_NO_OPS_SIZE makes the library look like one built before ModelOps grew)."""
     header = os.path.abspath(header)
     stem = os.path.splitext(os.path.basename(header))[0]
     name = name or stem
@@ -108,7 +109,7 @@ def build_model(header, struct=None, name=None, host_sim=False, out_dir=None, fo
     obj_dir = os.path.join(OBJ_DIR, f"model_{name}{'_hostsim' if host_sim else ''}")
     os.makedirs(obj_dir, exist_ok=True)
     os.makedirs(os.path.dirname(lib), exist_ok=True)
-    tus = model_tus(struct, name, [f'-DI2C_TU_HEADER="{header}"']) + [("entry.o", "i2c_model_entry.hip", [f"-DI2C_PLUGIN_NAME={name}"])]
+    tus = model_tus(struct, name, [f'-DI2C_TU_HEADER="{header}"']) + [("entry.o", "i2c_model_entry.hip", [f"-DI2C_PLUGIN_NAME={name}"] + list(entry_defs))]
 
     def one(tu):
         obj, src, defs = tu

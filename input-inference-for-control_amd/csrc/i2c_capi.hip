@@ -3,6 +3,7 @@
 #include <dlfcn.h>
 
 #include <cmath>
+#include <cstddef>
 #include <mutex>
 
 #include "i2c_entry.hpp"
@@ -14,6 +15,7 @@ namespace {
 // published id need no lock.
 struct PluginEntry {
   const i2c::ModelOps* ops[3];  // I2C_F64, I2C_F32, I2C_F64_F32S (nullptr: that precision was not built)
+  size_t ops_bytes;             // how much of a table exists: sizeof(ModelOps) as the LIBRARY was compiled (i2c_model_ops_size)
 };  // (a library opened by i2c_load_model stays loaded for the life of the process: its handle is never closed once registered)
 PluginEntry g_plugins[I2C_MAX_PLUGIN_MODELS];
 int g_n_plugins = 0;
@@ -125,8 +127,11 @@ size_t i2c_workspace_bytes(int model_id, int dtype, int B, int T) {
   return ops ? (dtype == I2C_F32 ? 4 : 8) * ops->workspace_elems(B, T) : 0;  // the workspace is arithmetic-typed (fp64 in I2C_F64_F32S)
 }
 
-int i2c_register_model(int abi_version, const I2cModelOps* ops_f64, const I2cModelOps* ops_f32, const I2cModelOps* ops_f64s,
-                       I2cDims* dims_out) {
+// Entries appended to ModelOps after ABI v9 froze (rollout_eval): a table whose library does not state its size ends before them
+constexpr size_t OPS_BYTES_V9 = offsetof(i2c::ModelOps, rollout_eval);
+
+static int register_model(int abi_version, const I2cModelOps* ops_f64, const I2cModelOps* ops_f32, const I2cModelOps* ops_f64s,
+                          I2cDims* dims_out, size_t ops_bytes) {
   if (abi_version != I2C_ABI_VERSION || !ops_f64) return I2C_EINVAL;
   const i2c::ModelOps* t[3] = {reinterpret_cast<const i2c::ModelOps*>(ops_f64), reinterpret_cast<const i2c::ModelOps*>(ops_f32),
                                reinterpret_cast<const i2c::ModelOps*>(ops_f64s)};
@@ -142,9 +147,14 @@ int i2c_register_model(int abi_version, const I2cModelOps* ops_f64, const I2cMod
       return I2C_MODEL_PLUGIN_BASE + k;
     }
   if (g_n_plugins >= I2C_MAX_PLUGIN_MODELS) return I2C_ENOTSUP;
-  g_plugins[g_n_plugins] = PluginEntry{{t[0], t[1], t[2]}};
+  g_plugins[g_n_plugins] = PluginEntry{{t[0], t[1], t[2]}, ops_bytes};
   if (dims_out) *dims_out = d;
   return I2C_MODEL_PLUGIN_BASE + g_n_plugins++;
+}
+
+int i2c_register_model(int abi_version, const I2cModelOps* ops_f64, const I2cModelOps* ops_f32, const I2cModelOps* ops_f64s,
+                       I2cDims* dims_out) {
+  return register_model(abi_version, ops_f64, ops_f32, ops_f64s, dims_out, OPS_BYTES_V9);
 }
 
 int i2c_load_model(const char* path, I2cDims* dims_out) {
@@ -159,7 +169,9 @@ int i2c_load_model(const char* path, I2cDims* dims_out) {
     dlclose(h);
     return I2C_EINVAL;
   }
-  const int id = i2c_register_model(abi(), ops(I2C_F64), ops(I2C_F32), ops(I2C_F64_F32S), dims_out);
+  typedef size_t (*size_fn)(void);
+  size_fn size = (size_fn)dlsym(h, "i2c_model_ops_size");  // optional: a library built before the table grew has none
+  const int id = register_model(abi(), ops(I2C_F64), ops(I2C_F32), ops(I2C_F64_F32S), dims_out, size ? size() : OPS_BYTES_V9);
   if (id < 0) dlclose(h);  // (a library registered twice keeps its first handle: dlopen reference-counts)
   return id;
 }
@@ -214,6 +226,53 @@ int i2c_rollout(const I2cProblem* p, const void* post, int n_rollouts, int polic
                 const void* eps_x, const void* eps_u, void* xu, void* z, void* x_final, void* z_term, void* stream) {
   if (!post || n_rollouts < 1 || policy < 0 || policy > 2) return I2C_EINVAL;
   I2C_DISPATCH(p, rollout(p, post, n_rollouts, policy, eps_x0, eps_x, eps_u, xu, z, x_final, z_term, stream));
+}
+
+// parts = 0: the lane budget chunk_geometry uses, 65536 lanes over the batch
+static int eval_parts(const I2cProblem* p, const I2cRolloutEval* e) {
+  if (e->parts != 0) return e->parts;
+  const long want = (65536L + p->B - 1) / p->B;
+  return (int)(want < e->n_rollouts ? want : e->n_rollouts);
+}
+// what both calls refuse from the scalar fields
+static int check_eval(const I2cProblem* p, const I2cRolloutEval* e) {
+  if (!e || e->n_rollouts < 1 || e->policy < 0 || e->policy > 2) return I2C_EINVAL;
+  if (e->parts < 0 || e->parts > e->n_rollouts) return I2C_EINVAL;
+  const int rc = check_problem_shape(p);
+  if (rc != I2C_OK) return rc;
+  if ((uint64_t)e->first_trajectory + (uint64_t)p->B > 0x100000000ull) return I2C_EINVAL;
+  if (p->dtype != I2C_F64) return I2C_ENOTSUP;  // the sums are fp64
+  return I2C_OK;
+}
+
+size_t i2c_rollout_eval_workspace(const I2cProblem* p, const I2cRolloutEval* ev, int32_t* parts_out) {
+  if (check_eval(p, ev) != I2C_OK) return 0;
+  I2cDims d;
+  const i2c::ModelOps* ops = find_ops(p->model_id, I2C_F64);
+  if (!ops) return 0;
+  ops->dims(&d);
+  const int parts = eval_parts(p, ev), dd = d.nx + d.nu;
+  if (parts_out) *parts_out = parts;
+  return (size_t)parts * (size_t)p->T * (size_t)(dd + I2C_SYM(dd)) * (size_t)p->B * 8;
+}
+
+int i2c_rollout_eval(const I2cProblem* p, const void* post, const I2cRolloutEval* ev, void* stream) {
+  if (!post || !ev || !ev->cost) return I2C_EINVAL;
+  if ((ev->xu_cov && !ev->xu_mean) || (ev->xu_mean && !ev->work)) return I2C_EINVAL;
+  int rc = check_eval(p, ev);
+  if (rc != I2C_OK) return rc;
+  rc = check_problem(p);
+  if (rc != I2C_OK) return rc;
+  if (p->model_id >= I2C_MODEL_PLUGIN_BASE) {  // a model library from before the entry existed: its tables end above it
+    const int k = p->model_id - I2C_MODEL_PLUGIN_BASE;
+    std::lock_guard<std::mutex> lock(g_plugin_mutex);
+    if (k >= g_n_plugins) return I2C_EINVAL;
+    if (g_plugins[k].ops_bytes < offsetof(i2c::ModelOps, rollout_eval) + sizeof(void*)) return I2C_ENOTSUP;
+  }
+  const i2c::ModelOps* ops = find_ops(p->model_id, p->dtype);
+  if (ops && p->model_params_b) ops = ops->per_traj;
+  if (!ops) return I2C_EINVAL;
+  return ops->rollout_eval(p, post, ev, eval_parts(p, ev), stream);
 }
 
 int i2c_riccati_sweep(const I2cProblem* p, const void* prior_out, const void* fwd, const void* xm, void* post, void* ric,

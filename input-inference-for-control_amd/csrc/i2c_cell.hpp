@@ -16,6 +16,7 @@
 #include "../../include/i2c_hip.h"
 #include "i2c_linalg.hpp"
 #include "i2c_models.hpp"
+#include "i2c_random.hpp"
 
 namespace i2c {
 
@@ -2528,34 +2529,123 @@ template <typename R> struct RolloutArgs {
                      // 2: expert, hard weight (ExpertTimeIndexedLinearGaussianPolicy, linear.py:46-90)
 };
 
+// Where a rollout's standard normals come from is a compile-time choice of the body: the caller's tensors (GivenNoise: i2c_rollout,
+// a NULL pointer switches that kind off), or per kind the caller's tensor where it is given and else the counter-based generator
+// of i2c_random.hpp (EvalNoise: i2c_rollout_eval). draw_*() readies the normals of one vector, x0() / x() / u() hand out element j.
+template <int NX, int NU, typename R, typename IDX> struct GivenNoise {
+  const R *e0, *ex, *eu;
+  long N;
+  IDX n;  // column of this rollout in the tensors
+  I2C_HD inline bool x0_on() const { return e0 != nullptr; }
+  I2C_HD inline bool x_on() const { return ex != nullptr; }
+  I2C_HD inline bool u_on() const { return eu != nullptr; }
+  I2C_HD inline void draw_x0() {}
+  I2C_HD inline void draw_x(int) {}
+  I2C_HD inline void draw_u(int) {}
+  I2C_HD inline R x0(const int j) const { return e0[(long)j * N + n]; }
+  I2C_HD inline R x(const int t, const int j) const { return ex[((long)t * NX + j) * N + n]; }
+  I2C_HD inline R u(const int t, const int j) const { return eu[((long)t * NU + j) * N + n]; }
+};
+template <int NX, int NU, typename R> struct EvalNoise {
+  GivenNoise<NX, NU, R, long> g;
+  uint64_t seed;
+  uint32_t traj, r;  // counter words 0 and 1: global trajectory, rollout
+  int bits;          // I2cRolloutEval.noise
+  R z0[NX], zx[NX], zu[NU];
+  I2C_HD inline bool x0_on() const { return g.e0 != nullptr || (bits & 4); }
+  I2C_HD inline bool x_on() const { return g.ex != nullptr || (bits & 1); }
+  I2C_HD inline bool u_on() const { return g.eu != nullptr || (bits & 2); }
+  I2C_HD inline void draw_x0() {
+    if (g.e0) {
+#pragma unroll
+      for (int j = 0; j < NX; ++j) z0[j] = g.x0(j);
+    } else {
+      normals<NX>(seed, traj, r, RNG_T_X0, RNG_X0, z0);
+    }
+  }
+  I2C_HD inline void draw_x(const int t) {
+    if (g.ex) {
+#pragma unroll
+      for (int j = 0; j < NX; ++j) zx[j] = g.x(t, j);
+    } else {
+      normals<NX>(seed, traj, r, (uint32_t)t, RNG_PROCESS, zx);
+    }
+  }
+  I2C_HD inline void draw_u(const int t) {
+    if (g.eu) {
+#pragma unroll
+      for (int j = 0; j < NU; ++j) zu[j] = g.u(t, j);
+    } else {
+      normals<NU>(seed, traj, r, (uint32_t)t, RNG_ACTION, zu);
+    }
+  }
+  I2C_HD inline R x0(const int j) const { return z0[j]; }
+  I2C_HD inline R x(int, const int j) const { return zx[j]; }
+  I2C_HD inline R u(int, const int j) const { return zu[j]; }
+};
+
+// What i2c_rollout_eval adds to a rollout (the ACCUMULATING sink of the body, against the row stores of i2c_rollout): the cost of
+// the rollout in a register, and the partial moment sums of the lane's part.
+template <typename R> struct EvalArgs {
+  const R* z;    // [T][NZ][B] per-cell targets of the problem, or null (c.zg)
+  R* cost;       // [n_rollouts][B]
+  R* work;       // [parts][T][D + sym D][B] or null: S1 = sum delta, S2 = sum delta delta^T of each part, delta = (x, u) - planned mean
+  uint64_t seed;
+  uint32_t first_trajectory;
+  int noise, parts;
+};
+
+// y^T W y, W packed lower
+template <int N, typename R> I2C_FN R quad_form(const R* W, const R* y) {
+  R q = R(0);
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    R r = R(0);
+#pragma unroll
+    for (int j = 0; j < i; ++j) r += W[tri(i, j)] * y[j];
+    q += y[i] * (W[tri(i, i)] * y[i] + R(2) * r);
+  }
+  return q;
+}
+
 // HZ (per-trajectory horizons): rollout n runs trajectory n % B's horizon Tb; x_final and z_term are the state behind cell Tb - 1
-template <class M, typename R, bool HZ = false>
-I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, const int n, [[maybe_unused]] const int Tb = 0) {
+// EVAL (i2c_rollout_eval): the same steps with the noise of EvalNoise and the accumulating sink: `n` is the trajectory b, `r` the
+// rollout, `q` the lane's part, `first` says that this is the first rollout the lane adds to its part's sums (it STORES them, later
+// ones load, add and store: the workspace needs no clearing)
+template <class M, typename R, bool HZ = false, bool EVAL = false>
+I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, const int n, [[maybe_unused]] const int Tb = 0,
+                                [[maybe_unused]] const EvalArgs<R>* ev = nullptr, [[maybe_unused]] const int r = 0,
+                                [[maybe_unused]] const int q = 0, [[maybe_unused]] const bool first = true) {
   using C = Consts<M, R>;
   constexpr int NX = C::NX, NU = C::NU, NZ = C::NZ, NZT = C::NZT, D = C::D, NA1 = M::NA > 0 ? M::NA : 1;
   const long B = c.B, N = (long)a.n_rollouts * B;
-  const int b = n % c.B;
+  const int b = EVAL ? n : n % c.B;
   const int T = HZ ? Tb : c.T;
+  std::conditional_t<EVAL, EvalNoise<NX, NU, R>, GivenNoise<NX, NU, R, int>> nz;
+  if constexpr (EVAL) nz = {{a.eps_x0, a.eps_x, a.eps_u, N, (long)r * B + b}, ev->seed, ev->first_trajectory + (uint32_t)b, (uint32_t)r, ev->noise, {}, {}, {}};
+  else nz = {a.eps_x0, a.eps_x, a.eps_u, N, n};
+  [[maybe_unused]] R cost = R(0);
   R pb[C::NP1];
   const R* prm = c.params;
   if constexpr (is_per_traj<M>::value) prm = param_ptr<M::NP>(params_of(c, b), pb);  // rollout n runs trajectory n % B's plant
   R x[NX];
 #pragma unroll
   for (int i = 0; i < NX; ++i) x[i] = a.x0[i * B + b];
-  if (a.eps_x0) {
+  if (nz.x0_on()) {
     R L[sym(NX)], rinv[NX];
 #pragma unroll
     for (int i = 0; i < sym(NX); ++i) L[i] = a.sig_x0[i * B + b];
     chol<NX>(L, rinv);
+    nz.draw_x0();
 #pragma unroll
     for (int i = 0; i < NX; ++i)
 #pragma unroll
-      for (int j = 0; j <= i; ++j) x[i] += L[tri(i, j)] * a.eps_x0[(long)j * N + n];
+      for (int j = 0; j <= i; ++j) x[i] += L[tri(i, j)] * nz.x0(j);
   }
   R Le[sym(NX)], rinv_e[NX];  // chol(sig_eta), constant (a model with process_noise: refactored at every step)
 #pragma unroll
   for (int i = 0; i < sym(NX); ++i) Le[i] = c.sig_eta[i];
-  if (a.eps_x) chol<NX>(Le, rinv_e);
+  if (nz.x_on()) chol<NX>(Le, rinv_e);
 
   for (int t = 0; t < T; ++t) {
     const long es = c.post_es();
@@ -2592,15 +2682,16 @@ I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, 
         u[p] = row[(long)(NX + p) * es] + w * v;
       }
     }
-    if (a.eps_u) {  // u += chol(sigK) eps
+    if (nz.u_on()) {  // u += chol(sigK) eps
       R Lk[sym(NU)], rk[NU];
 #pragma unroll
       for (int k = 0; k < sym(NU); ++k) Lk[k] = row[(long)(C::E_PRI + NU + k) * es];
       chol<NU>(Lk, rk);
+      nz.draw_u(t);
 #pragma unroll
       for (int p = 0; p < NU; ++p)
 #pragma unroll
-        for (int q2 = 0; q2 <= p; ++q2) u[p] += Lk[tri(p, q2)] * a.eps_u[((long)t * NU + q2) * N + n];
+        for (int q2 = 0; q2 <= p; ++q2) u[p] += Lk[tri(p, q2)] * nz.u(t, q2);
     }
     R xu[D], sn[NA1], cs[NA1], zt[NZ], xn[NX];
 #pragma unroll
@@ -2611,44 +2702,180 @@ I2C_HD inline void rollout_body(const Consts<M, R>& c, const RolloutArgs<R>& a, 
     for (int q2 = 0; q2 < M::NA; ++q2) r_sincos(xu[M::ang(q2)], &sn[q2], &cs[q2]);
     M::observe(prm, xu, sn, cs, zt);
     M::dynamics(prm, xu, sn, cs, xn);
-    if (a.xu) {
+    if constexpr (EVAL) {  // the accumulating sink: this step's cost, and (x, u) - planned mean into the part's sums
 #pragma unroll
-      for (int i = 0; i < D; ++i) a.xu[((long)t * D + i) * N + n] = xu[i];
-    }
-    if (a.z) {
+      for (int k = 0; k < NZ; ++k) zt[k] -= ev->z ? ev->z[((long)c.row(t) * NZ + k) * B + b] : c.zg[k];
+      cost += quad_form<NZ>(c.QR, zt);
+      if (ev->work) {
+        R* w = ev->work + (((long)q * c.T + t) * (D + sym(D))) * B + b;
+        R dl[D];
 #pragma unroll
-      for (int i = 0; i < NZ; ++i) a.z[((long)t * NZ + i) * N + n] = zt[i];
+        for (int i = 0; i < D; ++i) dl[i] = xu[i] - row[(long)i * es];
+        if (first) {
+#pragma unroll
+          for (int i = 0; i < D; ++i) w[(long)i * B] = dl[i];
+#pragma unroll
+          for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) w[(long)(D + tri(i, j)) * B] = dl[i] * dl[j];
+        } else {
+#pragma unroll
+          for (int i = 0; i < D; ++i) w[(long)i * B] += dl[i];
+#pragma unroll
+          for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) w[(long)(D + tri(i, j)) * B] += dl[i] * dl[j];
+        }
+      }
+    } else {
+      if (a.xu) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) a.xu[((long)t * D + i) * N + n] = xu[i];
+      }
+      if (a.z) {
+#pragma unroll
+        for (int i = 0; i < NZ; ++i) a.z[((long)t * NZ + i) * N + n] = zt[i];
+      }
     }
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = xn[i];
-    if (a.eps_x) {
+    if (nz.x_on()) {
+      nz.draw_x(t);
       if constexpr (has_process_noise<M, R>::value) {  // x' = f(x, u) + chol(sig_eta + Q(x, u)) eps, factored in the lane at every step
         const bool ok = step_noise_factor<M, R>(c.sig_eta, prm, xu, sn, cs, Le);
 #pragma unroll
         for (int i = 0; i < NX; ++i)
 #pragma unroll
-          for (int j = 0; j <= i; ++j) x[i] += Le[tri(i, j)] * a.eps_x[((long)t * NX + j) * N + n];
+          for (int j = 0; j <= i; ++j) x[i] += Le[tri(i, j)] * nz.x(t, j);
 #pragma unroll
         for (int i = 0; i < NX; ++i) x[i] = ok ? x[i] : R(__builtin_nan(""));  // (not positive definite: this rollout's state is NaN from here on)
       } else {
 #pragma unroll
         for (int i = 0; i < NX; ++i)
 #pragma unroll
-          for (int j = 0; j <= i; ++j) x[i] += Le[tri(i, j)] * a.eps_x[((long)t * NX + j) * N + n];
+          for (int j = 0; j <= i; ++j) x[i] += Le[tri(i, j)] * nz.x(t, j);
       }
     }
   }
-  if (a.x_final) {
+  if constexpr (EVAL) {  // the terminal cost of a problem with Qf, then the one store
+    if (NZT > 0 && c.has_Qf) {
+      R sn[NA1], cs[NA1], zT[C::NZT1];
 #pragma unroll
-    for (int i = 0; i < NX; ++i) a.x_final[(long)i * N + n] = x[i];
+      for (int q2 = 0; q2 < M::NA; ++q2) r_sincos(x[M::ang(q2)], &sn[q2], &cs[q2]);
+      M::observe_terminal(prm, x, sn, cs, zT);
+#pragma unroll
+      for (int i = 0; i < NZT; ++i) zT[i] -= c.zg_term[i];
+      cost += quad_form<C::NZT1>(c.Qf, zT);
+    }
+    ev->cost[(long)r * B + b] = cost;
+  } else {
+    if (a.x_final) {
+#pragma unroll
+      for (int i = 0; i < NX; ++i) a.x_final[(long)i * N + n] = x[i];
+    }
+    if (NZT > 0 && a.z_term) {
+      R sn[NA1], cs[NA1], zT[C::NZT1];
+#pragma unroll
+      for (int q2 = 0; q2 < M::NA; ++q2) r_sincos(x[M::ang(q2)], &sn[q2], &cs[q2]);
+      M::observe_terminal(prm, x, sn, cs, zT);
+#pragma unroll
+      for (int i = 0; i < NZT; ++i) a.z_term[(long)i * N + n] = zT[i];
+    }
   }
-  if (NZT > 0 && a.z_term) {
-    R sn[NA1], cs[NA1], zT[C::NZT1];
+}
+
+// The reduction of i2c_rollout_eval: lane (t, b) adds the parts' sums of cell t in ascending part order and writes mean and covariance
+//   mean = mu + S1 / R,  cov = (S2 - S1 S1^T / R) / (R - 1)     (R = 1: NaN, as an unbiased estimate of one sample is);
+// the t = 0 lanes also do the cost statistics of their trajectory, two passes over cost[r * B + b] with r ascending. A trajectory
+// with a non-finite cost gets NaN statistics and the count of such rollouts in n_bad.
+template <typename R> struct EvalReduceArgs {
+  const R* post;
+  const R* work;    // null: no moments
+  const R* cost;    // [n_rollouts][B]
+  R* cost_stats;    // [4][B] or null
+  int32_t* n_bad;   // [B] or null
+  R* xu_mean;       // [T][D][B] or null
+  R* xu_cov;        // [T][sym D][B] or null
+  int n_rollouts, parts;
+};
+template <class M, typename R>
+I2C_HD inline void rollout_eval_reduce_body(const Consts<M, R>& c, const EvalReduceArgs<R>& a, const int t, const int b, const int Tb) {
+  using C = Consts<M, R>;
+  constexpr int D = C::D, E = D + sym(D);
+  const long B = c.B;
+  const int Rn = a.n_rollouts;
+  // (both loops below: U loads in flight, then the additions in ascending order -- one lane walks a long column, so what a step costs
+  // is the latency of its loads)
+  constexpr int U = 16;
+  if (t == 0 && (a.cost_stats || a.n_bad)) {
+    R s = R(0), lo = a.cost[b], hi = a.cost[b];
+    int bad = 0;
+    for (int r0 = 0; r0 < Rn; r0 += U) {
+      R v[U];
 #pragma unroll
-    for (int q2 = 0; q2 < M::NA; ++q2) r_sincos(x[M::ang(q2)], &sn[q2], &cs[q2]);
-    M::observe_terminal(prm, x, sn, cs, zT);
+      for (int k = 0; k < U; ++k) v[k] = a.cost[(long)(r0 + k < Rn ? r0 + k : Rn - 1) * B + b];
 #pragma unroll
-    for (int i = 0; i < NZT; ++i) a.z_term[(long)i * N + n] = zT[i];
+      for (int k = 0; k < U; ++k) {
+        if (r0 + k < Rn) {
+          s += v[k];
+          lo = v[k] < lo ? v[k] : lo;
+          hi = v[k] > hi ? v[k] : hi;
+          bad += (v[k] - v[k] == R(0)) ? 0 : 1;
+        }
+      }
+    }
+    const R mean = s / R(Rn);
+    R ss = R(0);
+    for (int r0 = 0; r0 < Rn; r0 += U) {
+      R v[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) v[k] = a.cost[(long)(r0 + k < Rn ? r0 + k : Rn - 1) * B + b];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const R dv = v[k] - mean;
+        if (r0 + k < Rn) ss += dv * dv;
+      }
+    }
+    const R nan = R(__builtin_nan(""));
+    if (a.cost_stats) {
+      a.cost_stats[b] = bad ? nan : mean;
+      a.cost_stats[B + b] = bad ? nan : ss / R(Rn - 1);
+      a.cost_stats[2 * B + b] = bad ? nan : lo;
+      a.cost_stats[3 * B + b] = bad ? nan : hi;
+    }
+    if (a.n_bad) a.n_bad[b] = bad;
+  }
+  if (!a.work || !a.xu_mean || t >= Tb) return;
+  R S[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) S[e] = a.work[((long)t * E + e) * B + b];
+  constexpr int UP = E <= 9 ? 8 : (E <= 20 ? 4 : (E <= 35 ? 2 : 1));  // parts in flight: UP * E loads
+  for (int q0 = 1; q0 < a.parts; q0 += UP) {
+    R v[UP][E];
+#pragma unroll
+    for (int k = 0; k < UP; ++k) {
+      const R* w = a.work + (((long)(q0 + k < a.parts ? q0 + k : a.parts - 1) * c.T + t) * E) * B + b;
+#pragma unroll
+      for (int e = 0; e < E; ++e) v[k][e] = w[(long)e * B];
+    }
+#pragma unroll
+    for (int k = 0; k < UP; ++k) {
+      if (q0 + k < a.parts) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) S[e] += v[k][e];
+      }
+    }
+  }
+  const R* row = a.post + ((long)c.row(t) * C::E_POST) * B + c.post_bo(b);
+  const long es = c.post_es();
+  const R rn = R(Rn), rn1 = R(Rn - 1);
+#pragma unroll
+  for (int i = 0; i < D; ++i) a.xu_mean[((long)t * D + i) * B + b] = row[(long)i * es] + S[i] / rn;
+  if (a.xu_cov) {
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j) a.xu_cov[((long)t * sym(D) + tri(i, j)) * B + b] = (S[D + tri(i, j)] - S[i] * S[j] / rn) / rn1;
   }
 }
 

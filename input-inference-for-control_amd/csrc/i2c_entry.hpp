@@ -49,6 +49,9 @@ struct ModelOps {
                          void* stream);
   const ModelOps* per_traj;  // the same entry points with per-trajectory model parameters (I2cProblem.model_params_b); nullptr: NP = 0
   int (*plant_step)(const I2cProblem*, const PlantCall*, void* stream);  // (ABI v9)
+  // i2c_rollout_eval with `parts` resolved. The LAST entry, added without a new ABI version: a model library built before it has a
+  // table that ends above, says so by not exporting i2c_model_ops_size, and is never asked for it (i2c_capi.hip)
+  int (*rollout_eval)(const I2cProblem*, const void* post, const I2cRolloutEval*, int parts, void* stream);
 };
 
 // defined by the translation units generated from i2c_model_tu.hip

@@ -238,6 +238,28 @@ I2C_KERNEL(LANE_BLOCK) k_rollout_hz(I2C_LANE_PARAMS const Consts<M, R> c, const 
   if (n < (long)a.n_rollouts * c.B) rollout_body<M, R, true>(c, a, (int)n, clamp_horizon(hz[n % c.B], c.T));
 }
 
+// Monte-Carlo policy evaluation (i2c_rollout_eval): rollout_body with the generator's noise and the accumulating sink. A flat launch
+// of parts * B lanes, lane x = part q * B + trajectory b: lane (q, b) runs rollouts q, q + parts, ... of trajectory b in turn. (Flat,
+// not a part per grid row: a row of B = 1 would be a wavefront with one live lane -- measured, 65536 rollouts of one trajectory took
+// 50 ms that way -- and the grid's second dimension stops at 65535.) The lanes of a wavefront are consecutive b of one part, or the tail
+// of one part and the head of the next: every access of the [e][b] rows is one or two contiguous runs. Without moments parts =
+// n_rollouts: one lane per rollout. `hz`: the horizons, or null.
+template <class M, typename R>
+I2C_KERNEL(LANE_BLOCK) k_rollout_eval(I2C_LANE_PARAMS const Consts<M, R> c, const RolloutArgs<R> a, const EvalArgs<R> ev,
+                                      const int32_t* const hz) {
+  const long x = I2C_LANE_X(LANE_BLOCK);
+  const int q = (int)(x / c.B), b = (int)(x % c.B);
+  if (q >= ev.parts) return;
+  const int Tb = hz ? clamp_horizon(hz[b], c.T) : c.T;
+  for (long r = q; r < a.n_rollouts; r += ev.parts) rollout_body<M, R, true, true>(c, a, b, Tb, &ev, (int)r, q, r == q);
+}
+// ... and its reduction: lane (t, b), t the grid's second dimension (one row of lanes when there are no moments)
+template <class M, typename R>
+I2C_KERNEL(LANE_BLOCK) k_rollout_eval_reduce(I2C_LANE_PARAMS const Consts<M, R> c, const EvalReduceArgs<R> a, const int32_t* const hz) {
+  const long b = I2C_LANE_X(LANE_BLOCK);
+  if (b < c.B) rollout_eval_reduce_body<M, R>(c, a, I2C_LANE_Y, (int)b, hz ? clamp_horizon(hz[b], c.T) : c.T);
+}
+
 // Sum of the per-cell cost statistics over t: REDUCE_PARTS lanes per trajectory, fixed summation order; with `ms.alpha`
 // set (i2c_learn) the temperature M-step rides on it. The device form exchanges the partial sums through LDS; the host
 // form walks the same partition in the same order.
@@ -1907,6 +1929,26 @@ template <class M, typename R, typename S = R> struct Impl {
     return launch(k_rollout<M, R>, (long)n_rollouts * p->B, 1, LANE_BLOCK, stream, c, a);
   }
 
+  // i2c_rollout_eval: `parts` as i2c_capi.hip resolved it (1 .. n_rollouts); the arguments are checked there
+  static int rollout_eval(const I2cProblem* p, const void* post, const I2cRolloutEval* e, int parts, void* stream) {
+    if constexpr (MIXED || sizeof(R) != 8) {
+      return I2C_ENOTSUP;  // the sums are fp64
+    } else {
+      const C c = make_consts<M, R>(p, 0.0, 0);
+      if (p->horizons && horizons_supported(p) != I2C_OK) return horizons_supported(p);
+      RolloutArgs<R> a{(const R*)post, (const R*)p->x0, (const R*)p->sig_x0, (const R*)e->eps_x0, (const R*)e->eps_x,
+                       (const R*)e->eps_u, nullptr, nullptr, nullptr, nullptr, e->n_rollouts, e->policy};
+      const bool moments = e->xu_mean != nullptr;
+      EvalArgs<R> ev{(const R*)(c.z_per_cell ? p->z : nullptr), (R*)e->cost, moments ? (R*)e->work : nullptr, e->seed, e->first_trajectory,
+                     e->noise, moments ? parts : e->n_rollouts};
+      int rc = launch(k_rollout_eval<M, R>, (long)ev.parts * p->B, 1, LANE_BLOCK, stream, c, a, ev, p->horizons);
+      if (rc != I2C_OK || (!moments && !e->cost_stats && !e->n_bad)) return rc;
+      EvalReduceArgs<R> ra{(const R*)post, ev.work, (const R*)e->cost, (R*)e->cost_stats, e->n_bad, (R*)e->xu_mean, (R*)e->xu_cov,
+                           e->n_rollouts, ev.parts};
+      return launch(k_rollout_eval_reduce<M, R>, p->B, moments ? p->T : 1, LANE_BLOCK, stream, c, ra, p->horizons);
+    }
+  }
+
   // One plant step of the closed MPC loop (i2c_plant_step, and every step of i2c_mpc_episode): plant_step_body, one lane per
   // trajectory for every model -- it is one dynamics, one observe and one measure evaluation, with nothing to share between lanes.
   static int plant_step(const I2cProblem* p, const PlantCall* k, void* stream) {
@@ -1979,7 +2021,7 @@ template <class M, typename R, typename S = R> const ModelOps* make_ops(const Mo
   static const ModelOps ops = {&I::forward, &I::backward,  &I::mstep,        &I::learn,           &I::ckf,
                                &I::rollout, &I::propagate, &I::riccati,   &I::mpc_step,        &fill_dims<M>,
                                &workspace_elems<M>, &I::plan, &I::shift, &I::family_of, &I::learn_propagate, per_traj,
-                               &I::plant_step};
+                               &I::plant_step, &I::rollout_eval};
   return &ops;
 }
 // ... the per-trajectory table itself: only models with parameters have one

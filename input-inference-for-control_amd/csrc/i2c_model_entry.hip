@@ -23,6 +23,11 @@ const ModelOps* I2C_PASTE3(ops_, I2C_PLUGIN_NAME, _f64s)();
 extern "C" {
 __attribute__((visibility("default"))) int i2c_model_abi_version(void) { return I2C_ABI_VERSION; }
 __attribute__((visibility("default"))) const char* i2c_model_name(void) { return I2C_STR(I2C_PLUGIN_NAME); }
+// How much of a table this library has (entries are appended to ModelOps without a new ABI version; a library without this symbol
+// ends where ABI v9 froze). -DI2C_NO_OPS_SIZE leaves it out: what a library built before it existed looks like (tests).
+#ifndef I2C_NO_OPS_SIZE
+__attribute__((visibility("default"))) size_t i2c_model_ops_size(void) { return sizeof(i2c::ModelOps); }
+#endif
 __attribute__((visibility("default"))) const I2cModelOps* i2c_model_ops(int dtype) {
   const i2c::ModelOps* ops = dtype == I2C_F64   ? i2c::I2C_PASTE3(ops_, I2C_PLUGIN_NAME, _f64)()
                              : dtype == I2C_F32 ? i2c::I2C_PASTE3(ops_, I2C_PLUGIN_NAME, _f32)()

@@ -1082,6 +1082,93 @@ class BatchedI2c:
                 res[k] = v.reshape(v.shape[0], R_, B).permute(1, 2, 0)  # (R, B, n)
         return res
 
+    def evaluate(self, n_rollouts, policy="linear", process_noise=True, action_noise=False, sample_x0=False, seed=0, moments=True,
+                 parts=None, first_trajectory=0, model_params=None, eps_x0=None, eps_x=None, eps_u=None, percentiles=(10, 90)):
+        """Monte-Carlo evaluation of the current controllers on the device (`i2c_rollout_eval`): n_rollouts simulations of every
+        trajectory through the noisy plant with noise drawn in the kernel (Philox4x32-10 keyed by `seed`, counter = (first_trajectory
+        + b, r, t, kind): include/i2c_hip.h), reduced there to
+            cost (R, B), cost_mean / cost_var (unbiased) / cost_min / cost_max (B,), cost_percentiles (len(percentiles), B)
+            (torch.quantile, linear interpolation as np.percentile), n_bad (B,) int32: rollouts with a non-finite cost (their
+            trajectory's statistics are NaN), xu_mean (B, T, d) and xu_cov (B, T, d, d) of (x_t, u_t) over the rollouts (None with
+            moments=False; rows beyond a trajectory's horizon are NaN: valid_cells()), parts: lanes per trajectory that summed them.
+        The cost is the problem's quadratic cost over all T_b steps plus the Qf term (i2c.utils.quadratic_trajectory_cost), NOT the
+        reference evaluator's convention. eps_x0 / eps_x / eps_u: GIVEN standard normals in i2c_rollout's layouts, each switching
+        its kind on and replacing the generator for it. model_params: (B, NP) plants for this call only, as in rollout().
+        A sharded caller passes first_trajectory = dist.shard_range(...)[0] and gets the draws of the unsharded batch."""
+        R_, B, T, dev, dt = int(n_rollouts), self.B, self.H, self.device, self.dtype
+        if policy not in ("linear", "expert", "expert_soft", "expert_hard"):
+            raise ValueError(f"policy must be linear, expert_soft or expert_hard, got {policy!r}")
+        code = {"linear": 0, "expert": 1, "expert_soft": 1, "expert_hard": 2}[policy]
+        if R_ < 1 or R_ >= 2 ** 31:
+            raise ValueError(f"n_rollouts must be in [1, 2^31), got {n_rollouts}")
+        if self.mixed or dt != torch.float64:
+            raise ValueError("evaluate() needs an fp64 engine: the sums are fp64")
+        P = 0 if parts is None else int(parts)
+        if parts is not None and not 1 <= P <= R_:
+            raise ValueError(f"parts must be in [1, n_rollouts = {R_}], got {parts}")
+        first = int(first_trajectory)
+        if first < 0 or first + B > 2 ** 32:
+            raise ValueError(f"first_trajectory + B must fit 32 bits, got {first_trajectory} + {B}")
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+        qs = [float(q) for q in percentiles]
+        if any(not 0.0 <= q <= 100.0 for q in qs):
+            raise ValueError(f"percentiles must be in [0, 100], got {percentiles}")
+        N = R_ * B
+        given = lambda t, shape: None if t is None else torch.as_tensor(t, dtype=dt, device=dev).reshape(shape).contiguous()  # noqa: E731
+        eps_x0, eps_x, eps_u = given(eps_x0, (self.nx, N)), given(eps_x, (T, self.nx, N)), given(eps_u, (T, self.nu, N))
+        problem, plant = self._problem, None
+        if model_params is not None:
+            plant = self._params_to_device(model_params)
+            problem = self._make_problem()
+            problem.model_params_b = plant.data_ptr()
+        ev = _native.I2cRolloutEval()
+        ev.n_rollouts, ev.policy, ev.parts, ev.seed, ev.first_trajectory = R_, code, P, seed, first
+        ev.noise = ((_native.NOISE_PROCESS if process_noise else 0) | (_native.NOISE_ACTION if action_noise else 0) |
+                    (_native.NOISE_X0 if sample_x0 else 0))
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        ev.eps_x0, ev.eps_x, ev.eps_u = opt(eps_x0), opt(eps_x), opt(eps_u)
+        got = C.c_int32(0)
+        nbytes = self.lib.i2c_rollout_eval_workspace(C.byref(problem), C.byref(ev), C.byref(got))
+        if nbytes == 0:
+            raise ValueError("i2c_rollout_eval_workspace refused the request (see include/i2c_hip.h)")
+        cost = torch.empty(R_, B, dtype=dt, device=dev)
+        stats = torch.empty(4, B, dtype=dt, device=dev)
+        n_bad = torch.empty(B, dtype=torch.int32, device=dev)
+        xu_mean = xu_cov = None
+        if moments:
+            if getattr(self, "_eval_work", None) is None or self._eval_work.numel() != nbytes // 8:  # kept between calls of one shape
+                self._eval_work = torch.empty(nbytes // 8, dtype=dt, device=dev)
+            new = torch.empty if self._horizons is None else (lambda *s, **k: torch.full(s, float("nan"), **k))
+            xu_mean = new(T, self.d, B, dtype=dt, device=dev)
+            xu_cov = new(T, sym_size(self.d), B, dtype=dt, device=dev)
+            ev.work, ev.xu_mean, ev.xu_cov = self._eval_work.data_ptr(), xu_mean.data_ptr(), xu_cov.data_ptr()
+        ev.cost, ev.cost_stats, ev.n_bad = cost.data_ptr(), stats.data_ptr(), n_bad.data_ptr()
+        rc = self.lib.i2c_rollout_eval(C.byref(problem), self._ptr(self.post), C.byref(ev), self._stream())
+        self._check(rc, "i2c_rollout_eval")
+        q = torch.as_tensor(qs, dtype=dt, device=dev) / 100.0
+        return {
+            "cost": cost, "cost_mean": stats[0], "cost_var": stats[1], "cost_min": stats[2], "cost_max": stats[3],
+            "cost_percentiles": self._cost_quantiles(cost, q),
+            "n_bad": n_bad,
+            "xu_mean": None if xu_mean is None else xu_mean.permute(2, 0, 1),
+            "xu_cov": None if xu_cov is None else unpack_sym(xu_cov.permute(2, 0, 1), self.d),
+            "parts": int(got.value),
+        }
+
+    @staticmethod
+    def _cost_quantiles(cost, q):
+        """Quantiles q (in [0, 1]) over the rollouts of cost (R, B), linear interpolation between order statistics."""
+        if q.numel() == 0:
+            return cost.new_empty(0, cost.shape[1])
+        if cost.numel() <= 2 ** 24:  # (torch.quantile's input limit)
+            return torch.quantile(cost, q, dim=0)
+        s, pos = cost.sort(0).values, q * (cost.shape[0] - 1)
+        lo = pos.floor().long()
+        hi = (lo + 1).clamp(max=cost.shape[0] - 1)
+        return s[lo] + (s[hi] - s[lo]) * (pos - lo.to(pos.dtype))[:, None]
+
     def _terminal_kl(self):
         """mvn_kl_divergence(x3_pf[T-1] || terminal prior) (i2c.py:1012-1019, 1223-1229)."""
         nx = self.nx
