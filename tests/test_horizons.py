@@ -35,7 +35,8 @@ LINEAR_PRIOR = ("em_linear_T60", 10, "terminal_prior", [1, 4, 10])    # a termin
 LINEAR_PRIOR_ONLY = ("em_linear_T60", 10, "terminal_prior_only", [1, 4, 10])
 PENDULUM_PROP = ("em_pendulum_T200", 12, "propagate", [1, 2, 7, 12, 12])
 # (detail, summary) tolerances on the GPU: what tests/test_hip_parity.py gives the same golden
-GPU_TOL = {"em_pendulum_T200": (1e-8, 1e-7), "em_dcp_T60": (1e-6, 1e-5), "em_linear_T60": (1e-8, 1e-7)}
+GPU_TOL = {"em_pendulum_T200": (1e-8, 1e-7), "em_dcp_T60": (1e-6, 1e-5), "em_linear_T60": (1e-8, 1e-7),
+           "em_cartpole_T100": (1e-6, 1e-5), "em_quadrotor_T20": (1e-6, 1e-5)}
 FWD = parity.FWD
 PROP = ["mu_xu0_pf", "sig_xu0_pf", "mu_x3_pf", "sig_x3_pf"]
 
@@ -69,6 +70,8 @@ def make_engine(case, lib, device, x0, mu_u, horizon=None, keep_prior=True, **kw
                          meta["alpha"], meta["tol"], mu_u, case["sig_u"], case.get("mu_x_term"), case.get("sig_x_term"),
                          quad=tuple(meta["quad"]), x0=x0, device=device, lib=lib, keep_prior=keep_prior, keep_xm=True, keep_zpost=True, **kw)
     eng._propagate = bool(meta.get("propagate"))
+    if "use_expert_controller" in meta:
+        eng.use_expert_controller = bool(meta["use_expert_controller"])
     eng.cell_stats = torch.zeros(eng.H, 2, eng.B, dtype=eng.dtype, device=eng.device)  # (an optional output of the fused walk)
     return eng
 
@@ -96,9 +99,11 @@ def per_trajectory(eng):
     return out
 
 
-def solo_oracle(case, x0, mu_u, b, Tb):
+def solo_oracle(case, x0, mu_u, b, Tb, z=None):
+    """The oracle of trajectory b alone at its own horizon (z: (B, T, nz) per-cell targets of the batch, or None)."""
     meta = dict(case.meta, T=int(Tb))
-    return oracle_from_case(Case({**dict(case), "meta": np.array(json.dumps(meta)), "mu_u": mu_u[b, :Tb]}), x0=x0[b:b + 1])
+    over = {} if z is None else {"z_traj": z[b:b + 1, :Tb]}
+    return oracle_from_case(Case({**dict(case), "meta": np.array(json.dumps(meta)), "mu_u": mu_u[b, :Tb]}), x0=x0[b:b + 1], **over)
 
 
 def masked_rel_err(a, ref, valid):
@@ -110,16 +115,36 @@ def masked_rel_err(a, ref, valid):
 
 def run_vs_oracles(lib, device, spec, tol_d, tol_p, tol_s):
     name, T, variant, horizons = spec
-    case = cut_case(name, T, variant)
-    B = len(horizons)
+    compare_with_oracles(lib, device, cut_case(name, T, variant), horizons, tol_d, tol_p, tol_s, what=f"{name}/{variant}")
+
+
+def compare_with_oracles(lib, device, case, horizons, tol_d, tol_p, tol_s, z=None, calibrate=False, what=""):
+    """Three EM iterations of a mixed batch against one oracle per trajectory, solved at that trajectory's horizon: every existing cell
+    of every per-cell output, the temperature, the M-step's statistics and the costs. z: (B, T, nz) per-cell targets. calibrate (cases
+    with propagation): calibrate_alpha() before the first iteration, the temperature against each oracle's calibrate_alpha()."""
+    T, B = case.meta["T"], len(horizons)
     x0, mu_u = parity.batched_inputs(case, B)
-    eng = make_engine(case, lib, device, x0, mu_u, horizons=horizons)
+    eng = make_engine(case, lib, device, x0, mu_u, horizons=horizons, z_traj=z)
     assert eng.forward_family == eng.backward_family == "lane" and eng.backward_schedule == "fused"
-    oras = [solo_oracle(case, x0, mu_u, b, Tb) for b, Tb in enumerate(horizons)]
+    oras = [solo_oracle(case, x0, mu_u, b, Tb, z) for b, Tb in enumerate(horizons)]
     valid = np_(eng.valid_cells()).astype(bool)
     assert valid.sum() == sum(horizons)
     prop = bool(case.meta.get("propagate"))
-    if prop:
+
+    def check_scalars(scalars, it):
+        for k, a, get in scalars:
+            ref = np.array([np.asarray(get(o)).reshape(-1)[0] for o in oras])
+            e = masked_rel_err(np_(a), ref, np.ones(B, bool))
+            print(f"{what} it{it} {k}: {e:.2e}")
+            assert e <= tol_s, f"{what} it{it} {k}: {e:.2e} > {tol_s:.0e}"
+
+    if calibrate:
+        assert prop
+        eng.calibrate_alpha()
+        for o in oras:
+            o.calibrate_alpha()
+        check_scalars([("calibrated alpha", eng.alpha, lambda o: o.alpha)], 0)
+    elif prop:
         eng.propagate()
         for o in oras:
             o.propagate()
@@ -140,11 +165,11 @@ def run_vs_oracles(lib, device, spec, tol_d, tol_p, tol_s):
         for k in keys:
             e = masked_rel_err(np_(got[k]), padded(lambda o, k=k: getattr(o, k)), valid)
             tol = tol_p if k in ("K", "k", "sigK") else tol_d
-            print(f"{name}/{variant} it{it} {k}: {e:.2e}")
-            assert e <= tol, f"{name}/{variant} it{it} {k}: {e:.2e} > {tol:.0e}"
+            print(f"{what} it{it} {k}: {e:.2e}")
+            assert e <= tol, f"{what} it{it} {k}: {e:.2e} > {tol:.0e}"
         cost = np.stack([padded(lambda o, i=i: o._gaussian_cost(o.mu_z0_m, o.sig_z0_m)[i]) for i in (0, 1)], axis=-1)
         e = masked_rel_err(np_(got["cell_cost"]), cost, valid)
-        assert e <= tol_d, f"{name}/{variant} it{it} cell_stats: {e:.2e}"
+        assert e <= tol_d, f"{what} it{it} cell_stats: {e:.2e}"
         scalars = [("alpha", eng.alpha, lambda o: o.alpha), ("alpha_hat", eng.stats_out[0], lambda o: o.alphas_desired[-1]),
                    ("alpha_new", eng.stats_out[1], lambda o: o.alphas[-1]), ("cost", eng.stats_out[2], lambda o: o.costs_m[-1]),
                    ("cost_var", eng.stats_out[3], lambda o: o.costs_m_var[-1])]
@@ -153,12 +178,9 @@ def run_vs_oracles(lib, device, spec, tol_d, tol_p, tol_s):
                         ("alpha_pf", eng.alphas_pf[-1], lambda o: o.alphas_pf[-1])]
         if eng.has_x_terminal:
             scalars += [("kl", eng.kl_terms[-1], lambda o: o.kl_terms[-1])]
-        for what, a, get in scalars:
-            ref = np.array([np.asarray(get(o)).reshape(-1)[0] for o in oras])
-            e = masked_rel_err(np_(a), ref, np.ones(B, bool))
-            print(f"{name}/{variant} it{it} {what}: {e:.2e}")
-            assert e <= tol_s, f"{name}/{variant} it{it} {what}: {e:.2e} > {tol_s:.0e}"
+        check_scalars(scalars, it)
     assert eng.failures() == []
+    return eng
 
 
 ORACLE_CASES = [PENDULUM, DCP, LINEAR_PRIOR, LINEAR_PRIOR_ONLY, PENDULUM_PROP]
@@ -219,29 +241,33 @@ CELL_KEYS = set(FWD + PROP + ["mu_xu0_m", "sig_xu0_m", "K", "k", "sigK", "mu_x3_
                               "mu_xu0_f", "sig_xu0_f"])
 
 
-def solved(case, lib, device, x0, mu_u, horizons, horizon=None, n_iter=2):
-    eng = make_engine(case, lib, device, x0, mu_u, horizon=horizon, horizons=horizons)
+def solved(case, lib, device, x0, mu_u, horizons, horizon=None, n_iter=2, **kw):
+    eng = make_engine(case, lib, device, x0, mu_u, horizon=horizon, horizons=horizons, **kw)
     for _ in range(n_iter):
         eng.learn_msgs()
     assert eng.failures() == []
     return eng
 
 
-def run_lane_independence(lib, device, name, T, B, tail, picks):
-    case = cut_case(name, T)
+def run_lane_independence(lib, device, name, T, B, tail, picks, variant=None, z=None, params=None):
+    """z: (B, T, nz) per-cell targets, params: (B, NP) per-trajectory model parameters -- each picked trajectory is solved alone with
+    its own rows of both, and the permutation permutes them with the rest."""
+    case = cut_case(name, T, variant)
     horizons = [i % 5 + 1 for i in range(64)] + tail
     assert len(horizons) == B
     x0, mu_u = parity.batched_inputs(case, B)
-    eng = solved(case, lib, device, x0, mu_u, horizons)
+    rows = lambda idx, Tb=T: {**({} if z is None else {"z_traj": z[idx, :Tb]}),  # noqa: E731
+                              **({} if params is None else {"model_params": params[idx]})}
+    eng = solved(case, lib, device, x0, mu_u, horizons, **rows(slice(None)))
     cells, traj = per_cell(eng), per_trajectory(eng)
     for b in picks:
         Tb = horizons[b]
-        solo = solved(case, lib, device, x0[b:b + 1], mu_u[b:b + 1, :Tb], [Tb], horizon=Tb)
+        solo = solved(case, lib, device, x0[b:b + 1], mu_u[b:b + 1, :Tb], [Tb], horizon=Tb, **rows(slice(b, b + 1), Tb))
         assert_same_bits({k: v[b] for k, v in cells.items()}, per_cell(solo), Tb, f"{name} b={b} T_b={Tb}")
         assert_same_bits({k: v[b] for k, v in traj.items()}, per_trajectory(solo), Tb, f"{name} b={b} T_b={Tb}")
     # permuting the batch permutes the results
     perm = np.random.default_rng(7).permutation(B)
-    other = solved(case, lib, device, x0[perm], mu_u[perm], [horizons[i] for i in perm])
+    other = solved(case, lib, device, x0[perm], mu_u[perm], [horizons[i] for i in perm], **rows(perm))
     valid = other.valid_cells()
     p = torch.as_tensor(perm, device=eng.device)
     assert torch.equal(valid, eng.valid_cells()[p])
@@ -293,13 +319,14 @@ def test_gpu_all_horizons_equal_to_T(hip, spec):
 
 
 # ---- 5 -----------------------------------------------------------------------------------------------------------------------------
-def run_canaries(lib, device, spec):
+def run_canaries(lib, device, spec, z=None):
+    """z: (B, T, nz) per-cell targets; None: the model's own target in every cell of every trajectory"""
     name, T, _, horizons = spec
     case = cut_case(name, T, "propagate")
     B = len(horizons)
     x0, mu_u = parity.batched_inputs(case, B)
     zg = np.asarray(parity.product_model(case).zg, float).reshape(-1)
-    eng = make_engine(case, lib, device, x0, mu_u, horizons=horizons, z_traj=np.broadcast_to(zg, (B, T, zg.size)))
+    eng = make_engine(case, lib, device, x0, mu_u, horizons=horizons, z_traj=np.broadcast_to(zg, (B, T, zg.size)) if z is None else z)
     eng.prop = torch.zeros(T, eng.dims.e_prop, B, dtype=eng.dtype, device=eng.device)
     eng.prop_stats = torch.zeros(3, B, dtype=eng.dtype, device=eng.device)
     valid = eng.valid_cells()
@@ -414,6 +441,13 @@ def test_resolver_with_horizons():
     # general cubature weights are served; terminal_cell = -1 (no terminal update) as well
     assert sched(shape(0, quad_alpha=1.2, quad_beta=0.44, quad_kappa=0.5)) == N.BWD_FUSED
     assert sched(shape(0, terminal_cell=-1)) == N.BWD_FUSED
+    # ... on every served model, also the rule whose weights do not sum to one (tests/test_horizons_options.py solves with both)
+    for model_id in (0, 2, 3, 4, 6):
+        for qa, qb, qk in ((1.2, 0.44, 0.5), (1.05, 0.0, 0.3)):
+            for lanes in (0, -1):
+                p = shape(model_id, group_lanes=lanes, quad_alpha=qa, quad_beta=qb, quad_kappa=qk)
+                assert [fam(p, s) for s in (N.SWEEP_FORWARD, N.SWEEP_BACKWARD, N.SWEEP_PROPAGATE)] == [1, 1, 1], (model_id, qa, lanes)
+                assert sched(p) == N.BWD_FUSED, (model_id, qa, lanes)
     # without horizons nothing changes: the default schedule of a small batch is the chunked one
     assert sched(shape(0, B=4096, T=200, horizons=False)) == N.BWD_CHUNKED
 
