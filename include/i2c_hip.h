@@ -19,7 +19,15 @@
  *  - Every function returns 0 on success or a negative I2C_E* code for argument / launch errors.
  *    Per-trajectory numerical failures (a covariance that is not positive definite -- the
  *    reference raises LinAlgError from quadrature.py:17-24 or scipy) never abort the batch:
- *    they are recorded in status[b] = (reason << 16) | (t + 1) for the FIRST failing step.
+ *    they are recorded in status[b] = (reason << 16) | (t + 1), once: a word already in status[b] is never overwritten.
+ *    Which step the word names (tests/test_failure_words.py holds every kernel family to this):
+ *      - the SEQUENTIAL sweeps (forward, the fused backward walk, propagation, the filter step) record the FIRST failing stage
+ *        of the first failing cell, in the order the reference executes them. A family whose form of the cell does not contain
+ *        the stage that failed reports the next stage of the same cell that sees the matrix (the group kernels never factor
+ *        the prior joint of an identity observation: the test's COARSER_BY_CONSTRUCTION table lists every such case);
+ *      - the backward schedules that process cells CONCURRENTLY (pass 2 of two_pass, chunked) record I2C_FAIL_POSTERIOR and
+ *        A cell of that trajectory whose smoothed joint is not positive definite, not necessarily the first in sweep order.
+ *    A temperature alpha[b] that is not positive (or NaN) is I2C_FAIL_OBS_COV at the first cell that uses it.
  *  - The library keeps no global mutable state apart from the append-only table of out-of-tree models (i2c_register_model,
  *    mutex-guarded); calls on different streams are independent (tests/test_streams.py runs two engines on two streams).
  *    Nothing is allocated or freed by the library: every buffer is owned by the caller.

@@ -510,6 +510,15 @@ I2C_FN int fold_cell_failure(int fail, int cell_bad, int t) {
   const int reason = order == 0 ? 2 : (order == 1 ? 1 : order + 1);
   return (fail == 0 && cell_bad != 0) ? ((reason << 16) | (t + 1)) : fail;
 }
+// A temperature alpha <= 0 (or NaN) makes sig_z + alpha xi indefinite: the reference's la.solve(assume_a='pos') raises (i2c.py:398).
+// Update forms that only divide by alpha take it through this, so that their factorisation fails on the NaN (one compare and select).
+template <typename R> I2C_FN R positive_or_nan(const R alpha) { return alpha > R(0) ? alpha : R(__builtin_nan("")); }
+// "The failed trajectory goes NaN" made explicit in what the lane, grid and group forward sweeps and the propagation kernels STORE:
+// a NaN that a failed pivot leaves in the ACTION part of a factor only (the last pivot of a joint) reaches the next cell through
+// the model functor alone, and a functor may drop it (the device's r_clip is v_max / v_min, which return the other operand;
+// r_min / r_max / r_where_gt drop one too). On the stored value, not the carried one: a select on the state mean sits on the
+// cell-to-cell dependency chain of a lone wave (measured: 1.8 % of the flagship benchmark).
+template <typename R> I2C_FN R nan_if(const bool bad, const R x) { return bad ? R(__builtin_nan("")) : x; }
 I2C_FN void set_status(int32_t* status, int b, int reason, int t) {
   if (status[b] == 0) status[b] = (reason << 16) | (t + 1);
 }
@@ -1183,7 +1192,8 @@ I2C_HD inline void forward_sweep_body(const Consts<M, R>& c, const FwdArgs<R, ST
     fail = fold_cell_failure(fail, cell_bad, t);
     if (wr) {
 #pragma unroll
-      for (int e = 0; e < NX; ++e) wst(out, VOFF ? 0u : (D + sym(D) + e) * rb, VOFF ? voff[D + sym(D) + e] : bo, (ST_)mu_x[e]);
+      for (int e = 0; e < NX; ++e)  // (e = 0: NaN in the rows of a failed trajectory from the failing cell on -- the STORED value only, see nan_if)
+        wst(out, VOFF ? 0u : (D + sym(D) + e) * rb, VOFF ? voff[D + sym(D) + e] : bo, (ST_)(e == 0 ? nan_if(fail != 0, mu_x[e]) : mu_x[e]));
 #pragma unroll
       for (int e = 0; e < sym(NX); ++e) wst(out, VOFF ? 0u : (D + sym(D) + NX + e) * rb, VOFF ? voff[D + sym(D) + NX + e] : bo, (ST_)sig_x[e]);
     }
@@ -2292,6 +2302,7 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
     for (int k = 0; k < NZ; ++k) zt_cur[k] = opaque(zt_cur[k]);
   }
   R sum_m = R(0), sum_v = R(0);
+  bool dead = false;  // this trajectory has failed at this or an earlier cell (see nan_if)
 
   // (HZ: the loop itself stays wave-uniform and a lane that is done sits the rest out -- leaving the loop lane by lane would keep a
   //  copy of everything that is live behind it, the state and the sums, per exit: scratch for the d >= 6 models)
@@ -2365,7 +2376,9 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
     R L0[sym(D)], rinv[D];
 #pragma unroll
     for (int e = 0; e < sym(D); ++e) L0[e] = S0[e];
-    if (!chol<D>(L0, rinv) && wr) set_status(a.status, b, 8, t);
+    const bool ok0 = chol<D>(L0, rinv);
+    if (!ok0 && wr) set_status(a.status, b, 8, t);
+    dead = dead || !ok0;
     R zt[NZ], mz[NZ], Sz[sym(NZ)];
 #pragma unroll
     for (int k = 0; k < NZ; ++k) zt[k] = ZPRE ? zt_cur[ZPRE ? k : 0] : (c.z_per_cell ? a.z[((long)c.row(t) * NZ + k) * B + b] : c.zg[k]);
@@ -2387,7 +2400,7 @@ I2C_HD inline void propagate_body(const Consts<M, R>& c, const PropArgs<R>& a, c
     }
     if (wr) {
 #pragma unroll
-      for (int e = 0; e < NX; ++e) out[(long)(D + sym(D) + e) * B] = mu_x[e];
+      for (int e = 0; e < NX; ++e) out[(long)(D + sym(D) + e) * B] = nan_if(dead, mu_x[e]);  // (rows of a failed trajectory: NaN from the failing cell on)
 #pragma unroll
       for (int e = 0; e < sym(NX); ++e) out[(long)(D + sym(D) + NX + e) * B] = sig_x[e];
     }

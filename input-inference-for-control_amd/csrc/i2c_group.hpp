@@ -960,7 +960,7 @@ I2C_HD inline void forward_group_body(const Consts<M, R>& c, const KC& kc, const
       cell_bad = flag_stage(cell_bad, g_kalman<NX, NT>(g, mu_x, sx, mzt, sztr, sxzt, &own), 5);
     }
     fail = fold_cell_failure(fail, cell_bad, t);
-    out.st_if(r < NX, O_MU3 + r, g_sel<NX>(mu_x, r));
+    out.st_if(r < NX, O_MU3 + r, nan_if(fail != 0, g_sel<NX>(mu_x, r)));  // (rows of a failed trajectory: NaN from the failing cell on, see nan_if)
 #pragma unroll
     for (int j = 0; j < NX; ++j)
       out.st_if(r < NX && j <= opaque_i(r), O_S3 + trx + j, sx[j]);
@@ -1259,6 +1259,7 @@ I2C_HD inline void propagate_group_body(const Consts<M, R>& c, const KC& kc, con
 #pragma unroll
   for (int j = 0; j < NX; ++j) sx[j] = a.sig_x0[(long)symidx(rx, trx, j) * B + b];
   R sum_m = R(0), sum_v = R(0);
+  bool dead = false;  // this trajectory has failed at this or an earlier cell (see nan_if, i2c_cell.hpp)
 
   for (int t = 0; t < T; ++t) {
     // Nothing that depends on the rank or on the row stride may be hoisted out of the time loop (the byte offsets of ~100
@@ -1312,7 +1313,9 @@ I2C_HD inline void propagate_group_body(const Consts<M, R>& c, const KC& kc, con
     R L0[D], rinv0[D];
 #pragma unroll
     for (int j = 0; j < D; ++j) L0[j] = s0[j];
-    if (!g_chol<D>(g, 0, L0, rinv0) && r == 0) set_status(a.status, b, 8, t);
+    const bool ok0 = g_chol<D>(g, 0, L0, rinv0);
+    if (!ok0 && r == 0) set_status(a.status, b, 8, t);
+    dead = dead || !ok0;
     R zt[NZ], mz[NZ], szr[NZ], cm, cv;
 #pragma unroll
     for (int k = 0; k < NZ; ++k) zt[k] = c.z_per_cell ? a.z[((long)c.row(t) * NZ + k) * B + b] : c.zg[k];
@@ -1334,7 +1337,7 @@ I2C_HD inline void propagate_group_body(const Consts<M, R>& c, const KC& kc, con
     g_transform<M, DenseStruct<D>, D, NX, false>(g, 0, 1, 2, c.rule_xu, mu0, L0, DynamicsF<M, R>{params_of(c, b)}, mu_x, sx, (R*)nullptr);
 #pragma unroll
     for (int l = 0; l < NX; ++l) sx[l] += c.rule_xu.W * kc.sig_eta[rx * NX + l];
-    out.st_if(r < NX, O_X3 + r, g_sel<NX>(mu_x, r));
+    out.st_if(r < NX, O_X3 + r, nan_if(dead, g_sel<NX>(mu_x, r)));  // (rows of a failed trajectory: NaN from the failing cell on)
 #pragma unroll
     for (int j = 0; j < NX; ++j)
       out.st_if(r < NX && j <= opaque_i(r), O_SX3 + trx + j, sx[j]);

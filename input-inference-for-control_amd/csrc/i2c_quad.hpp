@@ -1093,7 +1093,10 @@ I2C_HD inline void forward_quad_body(const Consts<M, R>& c, const KC& kc, const 
     // pivot algebra, identity blocks, triangle masks: ~25 fp64 values) is otherwise hoisted out of the time loop and pinned in
     // registers the cell needs for its 16 x 16 blocks -- they were spilled to scratch; recomputing one is a compare and a select
     const Quad<R> q = G::WIDE ? q_opaque(qw) : qw;
-    const R alpha = nx_alpha;
+    // a temperature that is not positive is the observation update's failure (reason 3: sig_z + alpha xi is not positive
+    // definite, i2c.py:398). The square-root form of that update never sees the sign of alpha, so the value is poisoned where it
+    // is used: every form of the update then fails on this cell and the trajectory goes NaN from here, as in the lane kernels
+    const R alpha = positive_or_nan(nx_alpha);
     const bool ff = w_uniform(nx_ff) != 0;
     R pmu[NBD], pj[NBD * NBD], kt[NBX], zt[NBZ];
 #pragma unroll
@@ -2885,7 +2888,7 @@ I2C_HD inline void propagate_quad_body(const Consts<M, R>& c, const KC& kc, cons
     }
 #pragma unroll
     for (int j = 0; j < NBX; ++j) {
-      out.st_if(live && r == 0, cc, O_X3 + 4 * j, mx[j]);
+      out.st_if(live && r == 0, cc, O_X3 + 4 * j, nan_if(fail != 0, mx[j]));  // (rows of a failed trajectory: NaN from the failing cell on)
 #pragma unroll
       for (int i = 0; i <= j; ++i) out.st_if(live && (i < j || r <= cc), sym_lane(i, j), O_SX3 + sym_k(i, j), sx[i * NBX + j]);
     }

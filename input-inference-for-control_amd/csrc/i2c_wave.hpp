@@ -593,7 +593,9 @@ I2C_HD inline void forward_wave_body(const Consts<M, R>& c, const KC& kc, const 
 #endif
   for (int t = 0; t < T; ++t) {
     const WIO<R, S> out = w_fwd_cell<R, S>(a.fwd, C::E_FWD, B, t, b);
-    const R alpha = nx_alpha, zt = c.z_per_cell ? nx_zt : kc.zg[j], pmu = nx_pmu;
+    // (positive_or_nan: the square-root form of the cost update never sees the sign of the temperature; a non-positive one fails
+    //  stage 2 of this cell -- reason 3 -- and the trajectory goes NaN from here, as in the lane kernels)
+    const R alpha = positive_or_nan(nx_alpha), zt = c.z_per_cell ? nx_zt : kc.zg[j], pmu = nx_pmu;
     // the sigma-point cell always scales the gain (i2c.py:366-375); Linearize: per-cell or graph-wide flag (i2c.py:259-265)
     const bool ff = w_uniform(nx_ff) != 0, scale_gain = LIN ? (a.expert ? w_uniform(nx_ex) != 0 : c.use_expert != 0) : true;
     R pj[4], kt[4];
