@@ -10,7 +10,6 @@ Device layout (see include/i2c_hip.h): every per-cell buffer is logically ``[T][
 posterior / prior and forward-message buffers are trajectory-major (``[T][B][E]``) behind permuted views.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -46,6 +45,14 @@ def unpack_sym(packed, n):
     return out
 
 
+def _addr(t):
+    """Device address of an optional tensor for a pointer field of a ctypes structure (None: NULL)."""
+    return None if t is None else t.data_ptr()
+
+
+POLICY_CODES = {"linear": 0, "expert": 1, "expert_soft": 1, "expert_hard": 2}  # the `policy` of i2c_rollout / I2cRolloutEval
+
+
 class I2cNumericalError(np.linalg.LinAlgError):
     """A covariance lost positive definiteness (the reference raises LinAlgError from
     np.linalg.cholesky / scipy, i2c/inference/quadrature.py:17-24)."""
@@ -68,6 +75,17 @@ class BatchedI2c:
                 f"library '{self.lib.build_info}' cannot run on device {self.device}: the HIP build needs a "
                 "GPU tensor device (there is no CPU fallback)"
             )
+        # (the request is resolved in two halves, around the cost model, so that every check keeps its place in the order)
+        backward_mode = self._resolve_kernels(model, horizon, dtype, storage_dtype, allow_inexact, inference, quad, group_lanes,
+                                              deterministic_family, backward_mode, overlap_propagation)
+        priors = self._set_cost_model(model, Q, R, Qf, alpha_update_tol, mu_u, sig_u, x0, sig_x0, batch)
+        self._resolve_inference(model, inference, gh_degree, quad, horizons, mu_x_terminal, sig_x_terminal, dtemp)
+        self._allocate(model, priors, alpha, z_traj, keep_zpost, keep_prior, keep_xm, keep_prior_joint, post_layout, backward_mode,
+                       model_params)
+
+    def _resolve_kernels(self, model, horizon, dtype, storage_dtype, allow_inexact, inference, quad, group_lanes,
+                         deterministic_family, backward_mode, overlap_propagation):
+        """Request, first half: precision, the model's dimensions, the kernel family asked for. Returns the backward mode to ask for."""
         # Precision. dtype = ARITHMETIC type: float64 is the reference's arithmetic and the only parity-grade one.
         #   storage_dtype=torch.float32 with dtype=torch.float64: the mixed mode I2C_F64_F32S -- fp64 arithmetic on fp32-STORED
         #     per-cell buffers (post, fwd, xm, zpost, prior_out); half the HBM bytes, deviation from fp64 bounded
@@ -139,7 +157,11 @@ class BatchedI2c:
             raise ValueError("fp32 storage (storage_dtype) is available for the cubature path only")
         if self.mixed and self.uses_group_kernels and not (dims.wave and self.group_lanes in (0, 64, _native.LANES_QUAD)):
             raise ValueError("fp32 storage (storage_dtype) is available for the one-lane, the quad and the wave kernels only")
+        return backward_mode
 
+    def _set_cost_model(self, model, Q, R, Qf, alpha_update_tol, mu_u, sig_u, x0, sig_x0, batch):
+        """The batch size, the priors broadcast to it (returned for _allocate: mu_u, x0, sig_x0, sig_u) and the cost model."""
+        T, nx, nu, nz, nzt = self.H, self.nx, self.nu, self.nz, self.nzt
         mu_u = np.asarray(mu_u, dtype=np.float64)
         if mu_u.ndim == 2:
             mu_u = mu_u[None]
@@ -182,6 +204,11 @@ class BatchedI2c:
             self.Qf = np.zeros((nx, nx))  # i2c.py:792
             self.sig_xi_terminal_base = None
         self.alpha_update_tol = float(alpha_update_tol)
+        return mu_u, x0, sig_x0, sig_u
+
+    def _resolve_inference(self, model, inference, gh_degree, quad, horizons, mu_x_terminal, sig_x_terminal, dtemp):
+        """Request, second half: the inference rule and what hangs on it (process noise, horizons, quadrature, terminal prior)."""
+        dims, dtype, nx, nu, nzt = self.dims, self.dtype, self.nx, self.nu, self.nzt
         # inference method of the E-step (I2cGraph's `inference`, i2c.py:103-127): "cubature" = sigma points with
         # CubatureQuadrature(*quad); "linearize" = Linearize(), whose plan cost and propagation use
         # CubatureQuadrature(1, 0, 0) (i2c.py:109-115, 841-844)
@@ -244,6 +271,12 @@ class BatchedI2c:
                             "mean its Linearize rule back-calculates (i2c.py:464-470) is not implemented here")
         self.dtemp = float(dtemp)
 
+    def _allocate(self, model, priors, alpha, z_traj, keep_zpost, keep_prior, keep_xm, keep_prior_joint, post_layout, backward_mode,
+                  model_params):
+        """The device buffers, the descriptor, and the resolver's two answers (backward schedule, kernel families) that size them."""
+        mu_u, x0, sig_x0, sig_u = priors
+        dims, T, B, nx, nu, nz, nzt = self.dims, self.H, self.B, self.nx, self.nu, self.nz, self.nzt
+        inference = self.inference
         dev, dt, st = self.device, self.dtype, self.store_dtype
         to = lambda a: torch.as_tensor(np.array(a, dtype=np.float64, order="C"), dtype=dt, device=dev)  # noqa: E731
         zeros = lambda *s: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
@@ -287,8 +320,10 @@ class BatchedI2c:
         self.e_term = 4 + nzt + sym_size(nzt)
         self.term_stats = zeros(self.e_term, B)
         self.stats_out = zeros(4, B)
-        self.prop = None
-        self.prop_stats = None
+        self.prop = self.prop_stats = None  # made on first use: _propagation_buffers()
+        self._loop_yu = self._eval_work = self._health = None  # (scratch of run_closed_loop, evaluate, iteration_health)
+        self._mpc_action = zeros(nu + sym_size(nu), B)  # where a control step leaves the first planned action's moments
+        self._minus_one = torch.full((B,), -1.0, dtype=dt, device=dev)  # costs_pf of an iteration without propagation (i2c.py:1065)
         self.x0 = to(x0.T)
         self.sig_x0 = to(pack_sym_np(sig_x0).T)
         self.alpha = to(np.broadcast_to(np.asarray(alpha, np.float64), (B,)))
@@ -360,7 +395,9 @@ class BatchedI2c:
         self._problem = self._make_problem()  # (now with the workspace)
 
     # ------------------------------------------------------------------ C-ABI plumbing
-    def _make_problem(self):
+    def _make_problem(self, plant_params_b=None):
+        """A descriptor of the engine as it is now. plant_params_b: a [NP][B] tensor that stands in for the engine's per-trajectory
+        model parameters (_plant_problem)."""
         p = I2cProblem()
         p.abi_version = _native.ABI_VERSION
         p.model_id = self.model_id
@@ -411,10 +448,11 @@ class BatchedI2c:
         p.alpha = self.alpha.data_ptr()
         p.alpha_cell = self.alpha_cell.data_ptr() if self.alpha_cell is not None else None
         p.temp = self.temp.data_ptr()
-        p.work = self.work.data_ptr() if getattr(self, "work", None) is not None else None
+        p.work = self.work.data_ptr() if self.work is not None else None
         p.feedforward = self.feedforward.data_ptr()
         p.expert = self.expert_cells.data_ptr() if self.expert_cells is not None else None
-        p.model_params_b = self._params_b.data_ptr() if self._params_b is not None else None
+        params_b = self._params_b if plant_params_b is None else plant_params_b
+        p.model_params_b = params_b.data_ptr() if params_b is not None else None
         p.horizons = self._horizons.data_ptr() if self._horizons is not None else None
         return p
 
@@ -463,14 +501,10 @@ class BatchedI2c:
         horizon keep whatever they held."""
         v = torch.as_tensor(self._check_horizons(h), dtype=torch.int32, device=self.device)
         self._horizons_np = v.cpu().numpy()
-        if self._horizons is None:
-            self._horizons = v
-            self.refresh_problem()
+        if self._install("_horizons", v):
             mode = self.lib.i2c_backward_schedule(C.byref(self._problem))
             self._check(0 if mode == _native.BWD_FUSED else (mode if mode < 0 else -1), "i2c_backward_schedule")
             self.fused_backward, self.backward_schedule = True, "fused"
-        else:
-            self._horizons.copy_(v)
 
     def valid_cells(self):
         """(B, T) bool mask of the cells that exist: cell t of trajectory b with t < horizons[b] (all of them without horizons)."""
@@ -507,12 +541,7 @@ class BatchedI2c:
     def set_model_params(self, params):
         """Replace the per-trajectory model parameters, (B, NP), in place (the device pointer stays: a payload that changes
         between MPC steps needs nothing else). An engine built without model_params gets its buffer here."""
-        v = self._params_to_device(params)
-        if self._params_b is None:
-            self._params_b = v
-            self.refresh_problem()
-        else:
-            self._params_b.copy_(v)
+        self._install("_params_b", self._params_to_device(params))
 
     def kernel_family(self, sweep="forward"):
         """Which kernel family serves a sweep of THIS problem ("lane", "group", "wave", "quad" or "grid"): i2c_kernel_family(), the library's
@@ -534,8 +563,45 @@ class BatchedI2c:
         return self.kernel_family("backward")
 
     def refresh_problem(self):
-        """Rebuild the C problem descriptor after changing host-side constants / tensors."""
+        """Rebuild the C problem descriptor after changing host-side constants / tensors (a new buffer, that is a new pointer)."""
         self._problem = self._make_problem()
+
+    def _install(self, name, value):
+        """A persistent buffer the descriptor points to takes `value`: copied in place where the buffer exists (the pointer stays),
+        else it becomes the buffer and the descriptor is rebuilt. Returns whether it was new."""
+        buf = getattr(self, name)
+        if buf is None:
+            setattr(self, name, value)
+            self.refresh_problem()
+        else:
+            buf.copy_(value)
+        return buf is None
+
+    def sync_problem(self):
+        """The one writer of the descriptor's mutable fields: they follow the engine's attributes. Runs before every library call
+        (_call) and in the methods that move the ring (for whoever reads `_problem` in between). Returns the descriptor."""
+        p = self._problem
+        p.expert_controller = int(bool(self.use_expert_controller))
+        p.t0 = int(self.t0)
+        p.terminal_cell = int(self.terminal_cell)
+        p.expert = None if self.expert_cells is None else self.expert_cells.data_ptr()
+        return p
+
+    def _call(self, name, *args, problem=None):
+        """Every library call that takes buffers: lib.<name>(&problem, *args, stream) with the descriptor up to date, tensors handed
+        over as pointers (None: NULL), a non-zero return code raised. problem: another descriptor (_plant_problem)."""
+        p = self.sync_problem() if problem is None else problem
+        rc = getattr(self.lib, name)(C.byref(p), *[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], self._stream())
+        if rc != 0:
+            self._check(rc, name)
+
+    def _plant_problem(self, plant_params):
+        """(descriptor, tensor to hold until the call is enqueued) of a call that runs on the PLANT's parameters (B, NP): a copy of
+        the descriptor with them as model_params_b. None: the engine's own."""
+        if plant_params is None:
+            return self.sync_problem(), None
+        plant = self._params_to_device(plant_params)
+        return self._make_problem(plant), plant
 
     def _stream(self):
         """The caller's current HIP stream on the engine's device (what torch.cuda.current_stream(device).cuda_stream returns, read
@@ -562,21 +628,15 @@ class BatchedI2c:
     # ------------------------------------------------------------------ sweeps
     def forward_sweep(self):
         """I2cGraph._forward_msgs (i2c.py:876-880)."""
-        self._problem.expert_controller = int(bool(self.use_expert_controller))
         if self.prior_out is not None:  # (the graph facade: the temperature THIS sweep ran at, for the cells' sig_z0_f = S_z + alpha xi)
             self.alpha_fwd = self.alpha.clone()
-        rc = self.lib.i2c_forward_sweep(C.byref(self._problem), self._ptr(self.prior), self._ptr(self.fwd),
-                                        self._ptr(self.prior_out), self._ptr(self.status), self._stream())
-        self._check(rc, "i2c_forward_sweep")
+        self._call("i2c_forward_sweep", self.prior, self.fwd, self.prior_out, self.status)
 
     def backward_sweep(self):
         """I2cGraph._backward_msgs (i2c.py:882-886) + per-cell M-step statistics."""
         if self.keep_prior_joint and self.post is self.prior:  # do not overwrite the prior of this sweep
             self.post, self._post_spare = self._post_spare, None
-        rc = self.lib.i2c_backward_sweep(C.byref(self._problem), self._ptr(self.fwd), self._ptr(self.xm),
-                                         self._ptr(self.post), self._ptr(self.zpost), self._ptr(self.cell_stats),
-                                         self._ptr(self.term_stats), self._ptr(self.status), self._stream())
-        self._check(rc, "i2c_backward_sweep")
+        self._call("i2c_backward_sweep", self.fwd, self.xm, self.post, self.zpost, self.cell_stats, self.term_stats, self.status)
 
     def forward_backward(self):
         """I2cGraph._forward_backward_msgs (i2c.py:1231-1236)."""
@@ -594,30 +654,29 @@ class BatchedI2c:
             raise RuntimeError("riccati_sweep() needs keep_prior=True and keep_xm=True")
         nx = self.nx
         self.ric = torch.zeros(self.H, nx + nx * nx, self.B, dtype=self.dtype, device=self.device)
-        rc = self.lib.i2c_riccati_sweep(C.byref(self._problem), self._ptr(self.prior_out), self._ptr(self.fwd),
-                                        self._ptr(self.xm), self._ptr(self.post), self._ptr(self.ric),
-                                        self._ptr(self.status), self._stream())
-        self._check(rc, "i2c_riccati_sweep")
+        self._call("i2c_riccati_sweep", self.prior_out, self.fwd, self.xm, self.post, self.ric, self.status)
         nu = self.ric[:, :nx].permute(2, 0, 1)
         lam = self.ric[:, nx:].permute(2, 0, 1).reshape(self.B, self.H, nx, nx)
         return nu, lam
 
     def propagate(self, _stats=None):
         """I2cGraph.propagate (i2c.py:1247-1251). (_stats: a [3][B] row that receives the statistics instead of self.prop_stats)"""
+        self._propagation_buffers()
+        self._call("i2c_propagate", self.post, self.prop, self.prop_stats if _stats is None else _stats,
+                   int(self.use_expert_controller), self.status)
+
+    def _propagation_buffers(self):
+        """prop ([T][e_prop][B]) and prop_stats ([3][B]: cost mean, cost variance, terminal KL), made on first use."""
         if self.prop is None:
             self.prop = torch.zeros(self.H, self.dims.e_prop, self.B, dtype=self.dtype, device=self.device)
             self.prop_stats = torch.zeros(3, self.B, dtype=self.dtype, device=self.device)
-        rc = self.lib.i2c_propagate(C.byref(self._problem), self._ptr(self.post), self._ptr(self.prop),
-                                    self._ptr(self.prop_stats if _stats is None else _stats), int(self.use_expert_controller),
-                                    self._ptr(self.status), self._stream())
-        self._check(rc, "i2c_propagate")
 
     def set_cell_expert(self, t, value):
         """cells[t].use_expert_controller = value (i2c.py:143): a per-cell flag like the reference's, allocated on first use
         (until then every cell follows `use_expert_controller`)."""
         if self.expert_cells is None:
             self.expert_cells = torch.full((self.H,), int(bool(self.use_expert_controller)), dtype=torch.uint8, device=self.device)
-            self._problem.expert = self.expert_cells.data_ptr()
+            self.sync_problem()
         self.expert_cells[(int(t) + self.t0) % self.H] = int(bool(value))
 
     def cell_expert(self, t):
@@ -641,16 +700,41 @@ class BatchedI2c:
         """calculate_alpha(sum of propagated observation covariances) (i2c.py:901-904, 934-939)."""
         return self.prop_stats[0] / (self.nz * self._cells_per_trajectory())
 
+    def _mstep(self, update_alpha):
+        """i2c_mstep on the statistics the last backward sweep left on the device -> a fresh [4][B] row: alpha_hat, alpha after the
+        clamp, cost mean, cost variance."""
+        self._call("i2c_mstep", self.term_stats, self.alpha_update_tol, int(bool(update_alpha)), self.stats_out)
+        return self.stats_out.clone()
+
+    def _record(self, mstep, prop=None, alphas=True, costs=True, alpha_pf=None, kl=None):
+        """The one writer of the per-iteration history: plain lists of (B,) device tensors. The entries are views of rows copied once
+        per iteration, and every costs_pf entry without propagation is the ONE constant row `_minus_one`: an entry of a history
+        list must never be mutated in place, only replaced (as calibrate_alpha() does with alphas[-1]).
+        mstep: [4][B] alpha_hat, alpha, cost mean, cost variance; prop: [3][B] propagated cost mean, variance, terminal KL, or None
+        without propagation. alphas / costs: which halves of the M-step row this caller records; alpha_pf, kl: the entries of
+        alphas_pf and kl_terms, where the caller has them."""
+        if costs:
+            self.costs_m.append(mstep[2])
+            self.costs_m_var.append(mstep[3])
+            if prop is None:
+                self.costs_pf.append(self._minus_one)
+            else:
+                self.costs_pf.append(prop[0])
+                self.costs_pf_var.append(prop[1])
+        if alpha_pf is not None:
+            self.alphas_pf.append(alpha_pf)
+        if alphas:
+            self.alphas_desired.append(mstep[0])
+            self.alphas.append(mstep[1])
+        if kl is not None:
+            self.kl_terms.append(kl)
+
     def alpha_mstep(self, update_alpha=True):
         """compute_update_alpha (i2c.py:921-963) alone: alpha_hat from the backward sweep's statistics, the clamp, and --
         with update_alpha -- the new temperature in every cell (update_xi). No cost bookkeeping, no prior update.
         Returns (alpha_hat, alpha after the clamp) as (B,) tensors and appends them to alphas_desired / alphas."""
-        rc = self.lib.i2c_mstep(C.byref(self._problem), self._ptr(self.term_stats), self.alpha_update_tol,
-                                int(bool(update_alpha)), self._ptr(self.stats_out), self._stream())
-        self._check(rc, "i2c_mstep")
-        out = self.stats_out.clone()
-        self.alphas_desired.append(out[0])
-        self.alphas.append(out[1])
+        out = self._mstep(update_alpha)
+        self._record(out, costs=False)
         if update_alpha:
             self._broadcast_alpha()
         return out[0], out[1]
@@ -659,44 +743,18 @@ class BatchedI2c:
         """I2cGraph.calc_cost (i2c.py:1045-1066) alone: the expected cost of the current posterior (and of the propagation) appended
         to the cost lists, from the statistics the last backward sweep / propagation left on the device. The temperature is not
         touched (the M-step kernel runs with update_alpha = 0)."""
-        rc = self.lib.i2c_mstep(C.byref(self._problem), self._ptr(self.term_stats), self.alpha_update_tol, 0,
-                                self._ptr(self.stats_out), self._stream())
-        self._check(rc, "i2c_mstep")
-        out = self.stats_out.clone()
-        self.costs_m.append(out[2])
-        self.costs_m_var.append(out[3])
-        if self._propagate:
-            ps = self.prop_stats.clone()
-            self.costs_pf.append(ps[0])
-            self.costs_pf_var.append(ps[1])
-        else:
-            self.costs_pf.append(torch.full_like(out[2], -1.0))  # i2c.py:1065
+        self._record(self._mstep(False), self.prop_stats.clone() if self._propagate else None, alphas=False)
 
     def maximize(self, update_alpha=True):
         """I2cGraph._maximize (i2c.py:1004-1019): cost, prior update, temperature M-step."""
-        rc = self.lib.i2c_mstep(C.byref(self._problem), self._ptr(self.term_stats), self.alpha_update_tol,
-                                int(bool(update_alpha)), self._ptr(self.stats_out), self._stream())
-        self._check(rc, "i2c_mstep")
-        out = self.stats_out.clone()
-        self.costs_m.append(out[2])
-        self.costs_m_var.append(out[3])
-        ps = None
-        if self._propagate:
-            ps = self.prop_stats.clone()  # ONE copy per iteration (cost mean, cost variance, terminal KL): the rows below are views
-            self.costs_pf.append(ps[0])
-            self.costs_pf_var.append(ps[1])
-            self.alphas_pf.append(ps[0] / (self.nz * self._cells_per_trajectory()))  # = _alpha_from_propagation()
-        else:
-            if getattr(self, "_minus_one", None) is None:
-                self._minus_one = torch.full_like(out[2], -1.0)  # (one constant row shared by every entry: no fill kernel per iteration)
-            self.costs_pf.append(self._minus_one)  # i2c.py:1065
+        out = self._mstep(update_alpha)
+        ps = self.prop_stats.clone() if self._propagate else None  # ONE copy per iteration: the recorded rows are views of it
         self.update_priors()
-        self.alphas_desired.append(out[0])
-        self.alphas.append(out[1])
         if update_alpha:
             self._broadcast_alpha()
-        if self.has_x_terminal:
-            self.kl_terms.append(ps[2].to(torch.float64) if (ps is not None and self.prop is not None) else self._terminal_kl())
+        # (the KL term is float64 here and of the engine's dtype from i2c_learn_propagate: only an fp32 engine can tell)
+        kl = (self._terminal_kl() if ps is None else ps[2].to(torch.float64)) if self.has_x_terminal else None
+        self._record(out, ps, alpha_pf=None if ps is None else ps[0] / (self.nz * self._cells_per_trajectory()), kl=kl)
 
     def learn_msgs(self):
         """One EM iteration (I2cGraph.learn_msgs, i2c.py:1238-1245)."""
@@ -706,70 +764,55 @@ class BatchedI2c:
             self.propagate()
         self.maximize()
 
+    def _learn_path(self, n_iters):
+        """How learn(n_iters) runs: "stepwise" (n x learn_msgs), "fused" (i2c_learn) or "propagate" (i2c_learn_propagate).
+        The library's loops update only alpha[b]; with per-cell temperatures (MPC) every cell has to take the new alpha each
+        iteration (update_xi, i2c.py:961-981), which the stepwise path does through _broadcast_alpha(). Separate prior / posterior
+        buffers (keep_prior_joint) need the host-side swap of update_priors(), kept priors (keep_prior) their alpha_fwd."""
+        if n_iters <= 0 or self.alpha_cell is not None or self.keep_prior_joint or self.prior_out is not None:
+            return "stepwise"
+        if not self._propagate:
+            return "fused"
+        # closed-loop propagation inside the loop: the one-lane kernels under the sigma-point rule with fp64 / fp32 storage = arithmetic
+        if self.mixed or self.uses_group_kernels or self.linearize or self.gauss_hermite:
+            return "stepwise"
+        return "propagate"
+
     def learn(self, n_iters):
-        """n_iters EM iterations enqueued from C++ with no host round trip (i2c_learn). Same results as
-        calling learn_msgs() n_iters times; available when closed-loop propagation is off."""
+        """n_iters EM iterations enqueued from C++ by ONE library call with no host round trip, the statistics of every iteration
+        written straight into history rows: i2c_learn, or with closed-loop propagation (covariance control, BASELINE config 5)
+        i2c_learn_propagate. The same numbers as n_iters x learn_msgs(), which is what runs where _learn_path() says so."""
         n_iters = int(n_iters)
-        # The fused loop updates only alpha[b]; with per-cell temperatures (MPC) every cell has to take the new alpha each
-        # iteration (update_xi, i2c.py:961-981), which the stepwise path does through _broadcast_alpha(). Separate prior /
-        # posterior buffers (keep_prior_joint) also need the host-side swap of update_priors().
-        if (self._propagate and n_iters > 0 and self.alpha_cell is None and not self.keep_prior_joint and self.prior_out is None
-                and not self.mixed and not self.uses_group_kernels and not self.linearize and not self.gauss_hermite):
-            return self._learn_with_propagation(n_iters)
-        if self._propagate or self.prior_out is not None or n_iters <= 0 or self.alpha_cell is not None or self.keep_prior_joint:
+        path = self._learn_path(n_iters)
+        if path == "stepwise":
             for _ in range(n_iters):
                 self.learn_msgs()
             return
-        self._problem.expert_controller = int(bool(self.use_expert_controller))
-        hist = torch.empty(n_iters, 4, self.B, dtype=self.dtype, device=self.device)
-        rc = self.lib.i2c_learn(C.byref(self._problem), self._ptr(self.post), self._ptr(self.fwd), self._ptr(self.xm),
-                                self._ptr(self.zpost), self._ptr(self.cell_stats), self._ptr(self.term_stats),
-                                self.alpha_update_tol, int(self.tau), n_iters, self._ptr(hist), self._ptr(self.status),
-                                self._stream())
-        self._check(rc, "i2c_learn")
+        hist = torch.empty(n_iters, 4, self.B, dtype=self.dtype, device=self.device)  # alpha_hat, alpha, cost mean, cost variance
+        sweeps = (self.post, self.fwd, self.xm, self.zpost, self.cell_stats, self.term_stats)
+        if path == "propagate":
+            return self._learn_with_propagation(n_iters, hist, sweeps)
+        self._call("i2c_learn", *sweeps, self.alpha_update_tol, int(self.tau), n_iters, hist, self.status)
         self.em_iter += n_iters
-        minus_one = torch.full((self.B,), -1.0, dtype=self.dtype, device=self.device)
+        kl = self._terminal_kl() if self.has_x_terminal else None  # (nothing it reads changes inside the loop: once per call)
         for it in range(n_iters):
-            self.alphas_desired.append(hist[it, 0])
-            self.alphas.append(hist[it, 1])
-            self.costs_m.append(hist[it, 2])
-            self.costs_m_var.append(hist[it, 3])
-            self.costs_pf.append(minus_one)
-            if self.has_x_terminal:
-                self.kl_terms.append(self._terminal_kl())
+            self._record(hist[it], kl=kl)
         self._broadcast_alpha()
 
-    def _learn_with_propagation(self, n_iters):
-        """n x learn_msgs() with closed-loop propagation (covariance control, BASELINE config 5) enqueued by ONE library call
-        (i2c_learn_propagate): forward, backward, propagate, M-step per iteration, the statistics of every iteration written
-        straight into history rows. From the second iteration on the propagation of iteration k shares a launch with the
-        forward sweep of iteration k + 1 (`overlap_propagation`; lane kernels of the d <= 5 models): the two chains of T dependent
-        cells become one (pendulum T=100, B=8192: 0.27 -> 0.19 ms per iteration). The same numbers as the one-by-one calls."""
-        if self.prop is None:
-            self.prop = torch.zeros(self.H, self.dims.e_prop, self.B, dtype=self.dtype, device=self.device)
-            self.prop_stats = torch.zeros(3, self.B, dtype=self.dtype, device=self.device)
-        hist = torch.empty(n_iters, 4, self.B, dtype=self.dtype, device=self.device)   # alpha_hat, alpha, cost mean, cost variance
+    def _learn_with_propagation(self, n_iters, hist, sweeps):
+        """learn() through i2c_learn_propagate: forward, backward, propagate, M-step per iteration. From the second iteration on the
+        propagation of iteration k shares a launch with the forward sweep of iteration k + 1 (`overlap_propagation`; lane kernels of
+        the d <= 5 models): the two chains of T dependent cells become one (pendulum T=100, B=8192: 0.27 -> 0.19 ms per iteration)."""
+        self._propagation_buffers()
         histp = torch.empty(n_iters, 3, self.B, dtype=self.dtype, device=self.device)  # propagated cost mean, variance, terminal KL
-        rc = self.lib.i2c_learn_propagate(C.byref(self._problem), self._ptr(self.post), self._ptr(self.fwd), self._ptr(self.xm),
-                                          self._ptr(self.zpost), self._ptr(self.cell_stats), self._ptr(self.term_stats),
-                                          self._ptr(self.prop), self._ptr(histp), self.alpha_update_tol, int(self.tau), n_iters,
-                                          self._ptr(hist), int(self.use_expert_controller), int(self.overlap_propagation),
-                                          self._ptr(self.status), self._stream())
-        self._check(rc, "i2c_learn_propagate")
+        self._call("i2c_learn_propagate", *sweeps, self.prop, histp, self.alpha_update_tol, int(self.tau), n_iters, hist,
+                   int(self.use_expert_controller), int(self.overlap_propagation), self.status)
         self.em_iter += n_iters
         self.stats_out.copy_(hist[-1])
         self.prop_stats.copy_(histp[-1])
         apf = histp[:, 0] / (self.nz * self._cells_per_trajectory())  # = _alpha_from_propagation() of every iteration
         for it in range(n_iters):
-            self.costs_m.append(hist[it, 2])
-            self.costs_m_var.append(hist[it, 3])
-            self.costs_pf.append(histp[it, 0])
-            self.costs_pf_var.append(histp[it, 1])
-            self.alphas_pf.append(apf[it])
-            self.alphas_desired.append(hist[it, 0])
-            self.alphas.append(hist[it, 1])
-            if self.has_x_terminal:
-                self.kl_terms.append(histp[it, 2])
+            self._record(hist[it], histp[it], alpha_pf=apf[it], kl=histp[it, 2] if self.has_x_terminal else None)
         self._broadcast_alpha()
 
     def calibrate_alpha(self, only_decrease=False):
@@ -799,11 +842,8 @@ class BatchedI2c:
         cov = self.sig_x0 if cov is None else cov
         ny = self.dims.ny
         assert y.shape == (ny, self.B) and u.shape == (self.nu, self.B) and y.dtype == self.dtype
-        zeta = (C.c_double * sym_size(ny))(*pack_sym_np(np.asarray(sig_zeta, np.float64)).reshape(-1))
         y, u = y.contiguous(), u.contiguous()  # bound to locals: a temporary copy must outlive the launch
-        rc = self.lib.i2c_ckf_filter(C.byref(self._problem), zeta, self._ptr(y), self._ptr(u),
-                                     self._ptr(mu), self._ptr(cov), self._ptr(self.status), self._stream())
-        self._check(rc, "i2c_ckf_filter")
+        self._call("i2c_ckf_filter", self._sig_zeta(sig_zeta, True), y, u, mu, cov, self.status)
         return mu, cov
 
     def enable_per_cell_alpha(self):
@@ -835,8 +875,7 @@ class BatchedI2c:
         self.t0 = (self.t0 + 1) % self.H
         if self.terminal_cell >= 0:
             self.terminal_cell -= 1
-        self._problem.t0 = int(self.t0)
-        self._problem.terminal_cell = int(self.terminal_cell)
+        self.sync_problem()
 
     def shift_horizon(self, z_new=None, want_action=False):
         """Receding horizon (mpc.py:174-181): drop cell 0, append a fresh feed-forward cell whose target is z_new ([nz][B]
@@ -846,14 +885,9 @@ class BatchedI2c:
         moments (mu_u (B, nu), sig_u packed (B, sym nu)) if want_action."""
         self._no_horizons("shift_horizon()")
         assert self.prior is self.post, "shift_horizon() between a sweep and its update_priors()"
-        if want_action and getattr(self, "_mpc_action", None) is None:
-            self._mpc_action = torch.empty(self.nu + sym_size(self.nu), self.B, dtype=self.dtype, device=self.device)
         if z_new is not None:
             z_new = z_new.contiguous()
-        rc = self.lib.i2c_shift_horizon(C.byref(self._problem), self._ptr(self.post), self._ptr(self.cell_init),
-                                        self._ptr(self.alpha_init), self._ptr(z_new),
-                                        self._ptr(self._mpc_action) if want_action else None, self._stream())
-        self._check(rc, "i2c_shift_horizon")
+        self._call("i2c_shift_horizon", self.post, self.cell_init, self.alpha_init, z_new, self._mpc_action if want_action else None)
         self._advance_ring()
         if want_action:
             return self._mpc_action[: self.nu].T, self._mpc_action[self.nu:].T
@@ -869,36 +903,31 @@ class BatchedI2c:
         st = _native.I2cMpcStep()
         st.do_filter = int(y is not None)
         if y is not None:
-            ny = self.dims.ny
-            assert y.shape == (ny, self.B) and u.shape == (self.nu, self.B) and y.dtype == self.dtype
-            for i, v in enumerate(pack_sym_np(np.asarray(sig_zeta, np.float64)).reshape(-1)):
-                st.sig_zeta[i] = float(v)
+            assert y.shape == (self.dims.ny, self.B) and u.shape == (self.nu, self.B) and y.dtype == self.dtype
             y, u = y.contiguous(), u.contiguous()
             st.y, st.u = y.data_ptr(), u.data_ptr()
-        self._fill_mpc_step(st, n_iter)
+        self._fill_mpc_step(st, n_iter, self._sig_zeta(sig_zeta, True) if y is not None else None)
         if z_new is not None:
             z_new = z_new.contiguous()
-        st.z_new = None if z_new is None else z_new.data_ptr()
-        self._problem.expert_controller = int(bool(self.use_expert_controller))
-        rc = self.lib.i2c_mpc_step(C.byref(self._problem), C.byref(st), self._stream())
-        self._check(rc, "i2c_mpc_step")
+        st.z_new = _addr(z_new)
+        self._call("i2c_mpc_step", C.byref(st))
         self._advance_ring()
         return self._mpc_action[: self.nu].T, self._mpc_action[self.nu:].T
 
     # ------------------------------------------------------------------ the closed loop on the device
-    def _fill_mpc_step(self, st, n_iter):
-        """The fields of I2cMpcStep every control step of this engine shares (buffers, tau, the action row)."""
+    def _fill_mpc_step(self, st, n_iter, zeta=None):
+        """The fields of I2cMpcStep every control step of this engine shares (buffers, tau, the action row), and the measurement
+        noise of a step that filters (zeta: what _sig_zeta() returned)."""
         st.n_iter, st.tau = int(n_iter), int(self.tau)
-        if getattr(self, "_mpc_action", None) is None:
-            self._mpc_action = torch.empty(self.nu + sym_size(self.nu), self.B, dtype=self.dtype, device=self.device)
         st.post, st.fwd = self.post.data_ptr(), self.fwd.data_ptr()
-        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        st.xm, st.zpost, st.cell_stats, st.term_stats = opt(self.xm), opt(self.zpost), opt(self.cell_stats), self.term_stats.data_ptr()
-        st.cell_init, st.alpha_init = self.cell_init.data_ptr(), opt(self.alpha_init)
+        st.xm, st.zpost, st.cell_stats, st.term_stats = _addr(self.xm), _addr(self.zpost), _addr(self.cell_stats), self.term_stats.data_ptr()
+        st.cell_init, st.alpha_init = self.cell_init.data_ptr(), _addr(self.alpha_init)
         st.action, st.status = self._mpc_action.data_ptr(), self.status.data_ptr()
+        if zeta is not None:
+            st.sig_zeta[: len(zeta)] = zeta[:]
 
     def _sig_zeta(self, sig_zeta, needed):
-        """The measurement noise (ny, ny): the argument, else sys.sig_zeta; packed (ctypes array) or None."""
+        """The measurement noise (ny, ny): the argument, else sys.sig_zeta; packed into a ctypes array, or None (an error if needed)."""
         if sig_zeta is None:
             sig_zeta = getattr(self.sys, "sig_zeta", None)
         if sig_zeta is None:
@@ -908,7 +937,7 @@ class BatchedI2c:
         ny = self.dims.ny
         sig_zeta = np.asarray(sig_zeta, np.float64)
         assert sig_zeta.shape == (ny, ny), f"sig_zeta must be ({ny}, {ny}), got {sig_zeta.shape}"
-        return pack_sym_np(sig_zeta).reshape(-1)
+        return (C.c_double * sym_size(ny))(*pack_sym_np(sig_zeta).reshape(-1))
 
     def _state_rows(self, a, n):
         """(B, n) / (n,) array or tensor -> a new contiguous [n][B] device tensor."""
@@ -917,6 +946,13 @@ class BatchedI2c:
             return a.expand(self.B, n).T.contiguous()
         a = np.broadcast_to(np.asarray(a, np.float64).reshape(-1, n), (self.B, n))
         return torch.as_tensor(np.array(a.T, order="C"), dtype=self.dtype, device=self.device)
+
+    def _noise(self, given, shape, draw=False, generator=None):
+        """Standard-normal samples of a simulation: the given ones (any array, taken in the kernels' layout `shape`), else drawn
+        here with torch.randn(generator=generator) if `draw`, else None (no noise of that kind)."""
+        if given is not None:
+            return torch.as_tensor(given, dtype=self.dtype, device=self.device).reshape(shape).contiguous()
+        return torch.randn(*shape, dtype=self.dtype, device=self.device, generator=generator) if draw else None
 
     def plant_step(self, x, u, sig_zeta=None, eps_x=None, eps_y=None, y_out=None, observe_state=False, z_ref=None, cost=None,
                    plant_params=None):
@@ -942,17 +978,9 @@ class BatchedI2c:
             assert y_out.shape == (ny, B) and y_out.is_contiguous() and y_out.dtype == self.dtype
         if cost is not None:
             assert cost.shape == (B,) and cost.is_contiguous() and cost.dtype == self.dtype
-        zeta = self._sig_zeta(sig_zeta, eps_y is not None)
-        zeta_c = None if zeta is None else (C.c_double * len(zeta))(*zeta)
-        problem, plant = self._problem, None
-        if plant_params is not None:
-            plant = self._params_to_device(plant_params)
-            problem = self._make_problem()
-            problem.model_params_b = plant.data_ptr()
-        rc = self.lib.i2c_plant_step(C.byref(problem), zeta_c, self._ptr(x), self._ptr(u), self._ptr(eps_x), self._ptr(eps_y),
-                                     self._ptr(y_out), self._ptr(self.x0) if observe_state else None, self._ptr(z_ref),
-                                     self._ptr(cost), self._stream())
-        self._check(rc, "i2c_plant_step")
+        problem, plant = self._plant_problem(plant_params)
+        self._call("i2c_plant_step", self._sig_zeta(sig_zeta, eps_y is not None), x, u, eps_x, eps_y, y_out,
+                   self.x0 if observe_state else None, z_ref, cost, problem=problem)
         return y_out
 
     def run_closed_loop(self, n_steps, n_iter, sig_zeta=None, x_true=None, process_noise=True, measurement_noise=True,
@@ -985,14 +1013,8 @@ class BatchedI2c:
         unknown = set(keep) - {"x", "u", "y", "mu"}
         if unknown or (observe_state and "y" in keep):
             raise ValueError(f"keep={keep!r}: any of 'x', 'u', 'y', 'mu' ('y' only when the state is not observed)")
-        rnd = lambda *s: torch.randn(*s, dtype=dt, device=dev, generator=generator)  # noqa: E731
-        given = lambda t, shape: torch.as_tensor(t, dtype=dt, device=dev).reshape(shape).contiguous()  # noqa: E731
-        eps_x = given(eps_x, (N, nx, B)) if eps_x is not None else (rnd(N, nx, B) if process_noise else None)
-        if observe_state:
-            eps_y = None
-        else:
-            eps_y = given(eps_y, (N, ny, B)) if eps_y is not None else (rnd(N, ny, B) if measurement_noise else None)
-        zeta = self._sig_zeta(sig_zeta, not observe_state)
+        eps_x = self._noise(eps_x, (N, nx, B), process_noise, generator)
+        eps_y = None if observe_state else self._noise(eps_y, (N, ny, B), measurement_noise, generator)
         x = self.x0.clone() if x_true is None else self._state_rows(x_true, nx)
         zt = None
         if z_traj is not None:
@@ -1002,11 +1024,8 @@ class BatchedI2c:
                 self.set_targets(z[:, np.minimum(np.arange(T), z.shape[1] - 1)])
             zt = torch.as_tensor(np.array(np.transpose(z, (1, 2, 0)), order="C"), dtype=dt, device=dev)
         st = _native.I2cMpcStep()
-        self._fill_mpc_step(st, n_iter)
-        if zeta is not None:
-            for i, v in enumerate(zeta):
-                st.sig_zeta[i] = float(v)
-        if getattr(self, "_loop_yu", None) is None:
+        self._fill_mpc_step(st, n_iter, self._sig_zeta(sig_zeta, not observe_state))
+        if self._loop_yu is None:
             self._loop_yu = torch.zeros(ny + nu, B, dtype=dt, device=dev)
         hist = {k: torch.empty(N, n, B, dtype=dt, device=dev) if k in keep else None
                 for k, n in (("x", nx), ("u", nu), ("y", ny), ("mu", nx))}
@@ -1014,17 +1033,16 @@ class BatchedI2c:
         plant = None if plant_params is None else self._params_to_device(plant_params)
         ep = _native.I2cEpisode()
         ep.n_steps, ep.observe_state, ep.n_z = N, int(bool(observe_state)), 0 if zt is None else int(zt.shape[0])
-        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        ep.x_true, ep.eps_x, ep.eps_y, ep.plant_params_b, ep.z_traj = x.data_ptr(), opt(eps_x), opt(eps_y), opt(plant), opt(zt)
+        ep.x_true, ep.eps_x, ep.eps_y, ep.plant_params_b, ep.z_traj = x.data_ptr(), _addr(eps_x), _addr(eps_y), _addr(plant), _addr(zt)
         ep.y, ep.u = self._loop_yu[:ny].data_ptr(), self._loop_yu[ny:].data_ptr()
-        ep.x_hist, ep.u_hist, ep.y_hist, ep.mu_hist = opt(hist["x"]), opt(hist["u"]), opt(hist["y"]), opt(hist["mu"])
+        ep.x_hist, ep.u_hist, ep.y_hist, ep.mu_hist = _addr(hist["x"]), _addr(hist["u"]), _addr(hist["y"]), _addr(hist["mu"])
         ep.cost = cost.data_ptr()
         ep.t0_out, ep.terminal_cell_out = int(self.t0), int(self.terminal_cell)
-        self._problem.expert_controller = int(bool(self.use_expert_controller))
-        rc = self.lib.i2c_mpc_episode(C.byref(self._problem), C.byref(st), C.byref(ep), self._stream())
-        self.t0, self.terminal_cell = int(ep.t0_out), int(ep.terminal_cell_out)  # where the call reports the ring, also after an error part-way
-        self._problem.t0, self._problem.terminal_cell = self.t0, self.terminal_cell
-        self._check(rc, "i2c_mpc_episode")
+        try:
+            self._call("i2c_mpc_episode", C.byref(st), C.byref(ep))
+        finally:  # where the call reports the ring, also after an error part-way
+            self.t0, self.terminal_cell = int(ep.t0_out), int(ep.terminal_cell_out)
+            self.sync_problem()
         out = {k: v.permute(2, 0, 1) for k, v in hist.items() if v is not None}
         out.update(cost=cost, x_true=x.T, eps_x=eps_x, eps_y=eps_y)
         return out
@@ -1035,11 +1053,7 @@ class BatchedI2c:
         zt = torch.as_tensor(np.array(np.transpose(z, (1, 2, 0)), order="C"), dtype=self.dtype, device=self.device)
         if self.t0:
             zt = torch.roll(zt, self.t0, 0)  # cell order -> ring rows
-        if self.z is None:
-            self.z = zt.contiguous()
-            self.refresh_problem()
-        else:
-            self.z.copy_(zt)
+        self._install("z", zt.contiguous())
 
     def rollout(self, n_rollouts=1, policy="linear", process_noise=True, action_noise=False, sample_x0=False,
                 generator=None, want=("xu", "z", "x_final", "z_term"), eps_x0=None, eps_x=None, eps_u=None, model_params=None):
@@ -1050,27 +1064,15 @@ class BatchedI2c:
         model_params: (B, NP) parameters of the PLANT for this rollout only (rollout n simulates row n % B), e.g. controllers
         planned on the nominal model evaluated on perturbed ones; None = the planning parameters."""
         N, T, dev, dt = int(n_rollouts) * self.B, self.H, self.device, self.dtype
-        code = {"linear": 0, "expert": 1, "expert_soft": 1, "expert_hard": 2}[policy]
-        rnd = lambda *s: torch.randn(*s, dtype=dt, device=dev, generator=generator)  # noqa: E731
-        given = lambda t, shape: torch.as_tensor(t, dtype=dt, device=dev).reshape(shape).contiguous()  # noqa: E731
-        eps_x0 = given(eps_x0, (self.nx, N)) if eps_x0 is not None else (rnd(self.nx, N) if sample_x0 else None)
-        eps_x = given(eps_x, (T, self.nx, N)) if eps_x is not None else (rnd(T, self.nx, N) if process_noise else None)
-        eps_u = given(eps_u, (T, self.nu, N)) if eps_u is not None else (rnd(T, self.nu, N) if action_noise else None)
-        out = {
-            "xu": torch.empty(T, self.d, N, dtype=dt, device=dev) if "xu" in want else None,
-            "z": torch.empty(T, self.nz, N, dtype=dt, device=dev) if "z" in want else None,
-            "x_final": torch.empty(self.nx, N, dtype=dt, device=dev) if "x_final" in want else None,
-            "z_term": torch.empty(self.nzt, N, dtype=dt, device=dev) if ("z_term" in want and self.nzt > 0) else None,
-        }
-        problem, plant = self._problem, None
-        if model_params is not None:
-            plant = self._params_to_device(model_params)
-            problem = self._make_problem()
-            problem.model_params_b = plant.data_ptr()
-        rc = self.lib.i2c_rollout(C.byref(problem), self._ptr(self.post), int(n_rollouts), code, self._ptr(eps_x0),
-                                  self._ptr(eps_x), self._ptr(eps_u), self._ptr(out["xu"]), self._ptr(out["z"]),
-                                  self._ptr(out["x_final"]), self._ptr(out["z_term"]), self._stream())
-        self._check(rc, "i2c_rollout")
+        code = POLICY_CODES[policy]
+        eps_x0 = self._noise(eps_x0, (self.nx, N), sample_x0, generator)
+        eps_x = self._noise(eps_x, (T, self.nx, N), process_noise, generator)
+        eps_u = self._noise(eps_u, (T, self.nu, N), action_noise, generator)
+        shapes = {"xu": (T, self.d, N), "z": (T, self.nz, N), "x_final": (self.nx, N), "z_term": (self.nzt, N)}
+        out = {k: torch.empty(*s, dtype=dt, device=dev) if (k in want and s[-2] > 0) else None for k, s in shapes.items()}
+        problem, plant = self._plant_problem(model_params)
+        self._call("i2c_rollout", self.post, int(n_rollouts), code, eps_x0, eps_x, eps_u, out["xu"], out["z"], out["x_final"],
+                   out["z_term"], problem=problem)
         R_, B = int(n_rollouts), self.B
         res = {"eps_x0": eps_x0, "eps_x": eps_x, "eps_u": eps_u}
         for k, v in out.items():
@@ -1096,9 +1098,9 @@ class BatchedI2c:
         its kind on and replacing the generator for it. model_params: (B, NP) plants for this call only, as in rollout().
         A sharded caller passes first_trajectory = dist.shard_range(...)[0] and gets the draws of the unsharded batch."""
         R_, B, T, dev, dt = int(n_rollouts), self.B, self.H, self.device, self.dtype
-        if policy not in ("linear", "expert", "expert_soft", "expert_hard"):
+        if policy not in POLICY_CODES:
             raise ValueError(f"policy must be linear, expert_soft or expert_hard, got {policy!r}")
-        code = {"linear": 0, "expert": 1, "expert_soft": 1, "expert_hard": 2}[policy]
+        code = POLICY_CODES[policy]
         if R_ < 1 or R_ >= 2 ** 31:
             raise ValueError(f"n_rollouts must be in [1, 2^31), got {n_rollouts}")
         if self.mixed or dt != torch.float64:
@@ -1116,19 +1118,13 @@ class BatchedI2c:
         if any(not 0.0 <= q <= 100.0 for q in qs):
             raise ValueError(f"percentiles must be in [0, 100], got {percentiles}")
         N = R_ * B
-        given = lambda t, shape: None if t is None else torch.as_tensor(t, dtype=dt, device=dev).reshape(shape).contiguous()  # noqa: E731
-        eps_x0, eps_x, eps_u = given(eps_x0, (self.nx, N)), given(eps_x, (T, self.nx, N)), given(eps_u, (T, self.nu, N))
-        problem, plant = self._problem, None
-        if model_params is not None:
-            plant = self._params_to_device(model_params)
-            problem = self._make_problem()
-            problem.model_params_b = plant.data_ptr()
+        eps_x0, eps_x, eps_u = self._noise(eps_x0, (self.nx, N)), self._noise(eps_x, (T, self.nx, N)), self._noise(eps_u, (T, self.nu, N))
+        problem, plant = self._plant_problem(model_params)
         ev = _native.I2cRolloutEval()
         ev.n_rollouts, ev.policy, ev.parts, ev.seed, ev.first_trajectory = R_, code, P, seed, first
         ev.noise = ((_native.NOISE_PROCESS if process_noise else 0) | (_native.NOISE_ACTION if action_noise else 0) |
                     (_native.NOISE_X0 if sample_x0 else 0))
-        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        ev.eps_x0, ev.eps_x, ev.eps_u = opt(eps_x0), opt(eps_x), opt(eps_u)
+        ev.eps_x0, ev.eps_x, ev.eps_u = _addr(eps_x0), _addr(eps_x), _addr(eps_u)
         got = C.c_int32(0)
         nbytes = self.lib.i2c_rollout_eval_workspace(C.byref(problem), C.byref(ev), C.byref(got))
         if nbytes == 0:
@@ -1138,15 +1134,14 @@ class BatchedI2c:
         n_bad = torch.empty(B, dtype=torch.int32, device=dev)
         xu_mean = xu_cov = None
         if moments:
-            if getattr(self, "_eval_work", None) is None or self._eval_work.numel() != nbytes // 8:  # kept between calls of one shape
+            if self._eval_work is None or self._eval_work.numel() != nbytes // 8:  # kept between calls of one shape
                 self._eval_work = torch.empty(nbytes // 8, dtype=dt, device=dev)
             new = torch.empty if self._horizons is None else (lambda *s, **k: torch.full(s, float("nan"), **k))
             xu_mean = new(T, self.d, B, dtype=dt, device=dev)
             xu_cov = new(T, sym_size(self.d), B, dtype=dt, device=dev)
             ev.work, ev.xu_mean, ev.xu_cov = self._eval_work.data_ptr(), xu_mean.data_ptr(), xu_cov.data_ptr()
         ev.cost, ev.cost_stats, ev.n_bad = cost.data_ptr(), stats.data_ptr(), n_bad.data_ptr()
-        rc = self.lib.i2c_rollout_eval(C.byref(problem), self._ptr(self.post), C.byref(ev), self._stream())
-        self._check(rc, "i2c_rollout_eval")
+        self._call("i2c_rollout_eval", self.post, C.byref(ev), problem=problem)
         q = torch.as_tensor(qs, dtype=dt, device=dev) / 100.0
         return {
             "cost": cost, "cost_mean": stats[0], "cost_var": stats[1], "cost_min": stats[2], "cost_max": stats[3],
@@ -1194,14 +1189,15 @@ class BatchedI2c:
         return 0.5 * (log_det_ratio + trace_ratio + dist - nx)
 
     # ------------------------------------------------------------------ failure reporting
-    def failures(self):
-        """Per-trajectory status words -> list of (b, reason, t) for failed trajectories."""
-        st = self.status.cpu().numpy()
-        return [(int(b), int(s) >> 16, (int(s) & 0xFFFF) - 1) for b, s in enumerate(st) if s != 0]
+    def failures(self, status=None):
+        """Per-trajectory status words (reason << 16 | cell + 1; 0 = fine) -> list of (b, reason, t) for failed trajectories.
+        status: a host copy of the words someone already fetched (iteration_health); default: read them now."""
+        status = self.status.cpu().numpy() if status is None else status
+        return [(int(b), int(s) >> 16, (int(s) & 0xFFFF) - 1) for b, s in enumerate(status) if s != 0]
 
     def raise_on_failure(self, status=None):
         """With B == 1 behave like the reference: raise; batched callers read `failures()`."""
-        f = self.failures() if status is None else [(int(b), int(s) >> 16, (int(s) & 0xFFFF) - 1) for b, s in enumerate(status) if s != 0]
+        f = self.failures(status)
         if f:
             b, reason, t = f[0]
             raise I2cNumericalError(f"trajectory {b}, cell {t}: {_native.FAIL_REASONS.get(reason, reason)}")
@@ -1209,17 +1205,18 @@ class BatchedI2c:
     def iteration_health(self):
         """(status (B,) int32, alpha_hat of the last M-step (B,) float64) on the host after ONE stream synchronisation: what a
         single-trajectory caller checks after every EM iteration (the reference raises inside the iteration: LinAlgError from a
-        Cholesky, "Alpha is NaN" from update_alpha, i2c.py:948-951). Two asynchronous copies into page-locked host memory."""
+        Cholesky, "Alpha is NaN" from update_alpha, i2c.py:948-951). Two asynchronous copies into page-locked host memory, which the
+        next call reuses: the arrays returned are copies the caller owns."""
         a = self.alphas_desired[-1]
         if self.device.type != "cuda":
             return self.status.numpy().copy(), a.to(torch.float64).numpy().copy()
-        if getattr(self, "_health", None) is None:
+        if self._health is None:
             self._health = (torch.empty(self.B, dtype=torch.int32).pin_memory(), torch.empty(self.B, dtype=self.dtype).pin_memory())
         hs, ha = self._health
         hs.copy_(self.status, non_blocking=True)
         ha.copy_(a, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
-        return hs.numpy(), ha.to(torch.float64).numpy()
+        return hs.numpy().copy(), ha.numpy().astype(np.float64)  # (astype copies)
 
     # ------------------------------------------------------------------ getters: (B, T, ...) tensors
     def _rows(self, buf, lo, n):

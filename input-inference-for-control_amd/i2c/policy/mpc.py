@@ -85,7 +85,7 @@ class MpcPolicy:
         e.status.zero_()
         e.terminal_cell = self._init_terminal
         e.t0 = self._init_t0  # rows were cloned in physical order, at this offset of the ring
-        e._problem.terminal_cell, e._problem.t0 = int(e.terminal_cell), int(e.t0)
+        e.sync_problem()
         self.xu_history, self.z_history = _LazyList(), _LazyList()
         self._belief_host = None
 
