@@ -70,6 +70,10 @@ class BatchedI2c:
             device = "cpu" if self.lib.is_host_sim else "cuda"
         self.device = torch.device(device)
         self._dev_index = None
+        # What a host-side view of the engine's results was made at (I2cGraph's cell views, the policies' belief): `revision` advances
+        # with every library call that takes buffers (_call) and every method that changes solver state from the host,
+        # `belief_revision` wherever x0 / sig_x0 are written. Plain ints: a view is fresh while the number it kept still holds.
+        self.revision = self.belief_revision = 0
         if self.lib.is_host_sim != (self.device.type == "cpu"):
             raise RuntimeError(
                 f"library '{self.lib.build_info}' cannot run on device {self.device}: the HIP build needs a "
@@ -570,6 +574,7 @@ class BatchedI2c:
         """A persistent buffer the descriptor points to takes `value`: copied in place where the buffer exists (the pointer stays),
         else it becomes the buffer and the descriptor is rebuilt. Returns whether it was new."""
         buf = getattr(self, name)
+        self.revision += 1
         if buf is None:
             setattr(self, name, value)
             self.refresh_problem()
@@ -590,6 +595,7 @@ class BatchedI2c:
     def _call(self, name, *args, problem=None):
         """Every library call that takes buffers: lib.<name>(&problem, *args, stream) with the descriptor up to date, tensors handed
         over as pointers (None: NULL), a non-zero return code raised. problem: another descriptor (_plant_problem)."""
+        self.revision += 1
         p = self.sync_problem() if problem is None else problem
         rc = getattr(self.lib, name)(C.byref(p), *[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], self._stream())
         if rc != 0:
@@ -634,9 +640,19 @@ class BatchedI2c:
 
     def backward_sweep(self):
         """I2cGraph._backward_msgs (i2c.py:882-886) + per-cell M-step statistics."""
-        if self.keep_prior_joint and self.post is self.prior:  # do not overwrite the prior of this sweep
-            self.post, self._post_spare = self._post_spare, None
+        self._split_posterior()  # do not overwrite the prior of this sweep
         self._call("i2c_backward_sweep", self.fwd, self.xm, self.post, self.zpost, self.cell_stats, self.term_stats, self.status)
+
+    def _split_posterior(self):
+        """keep_prior_joint, before a sweep writes the posterior: it goes to the spare buffer, the prior stays what the forward
+        sweep read. The inverse of _fold_posterior()."""
+        if self.keep_prior_joint and self.post is self.prior:
+            self.post, self._post_spare = self._post_spare, None
+
+    def _fold_posterior(self):
+        """The posterior becomes the prior (one buffer again); the old prior buffer is the spare one."""
+        if self.prior is not self.post:
+            self._post_spare, self.prior = self.prior, self.post
 
     def forward_backward(self):
         """I2cGraph._forward_backward_msgs (i2c.py:1231-1236)."""
@@ -678,6 +694,7 @@ class BatchedI2c:
             self.expert_cells = torch.full((self.H,), int(bool(self.use_expert_controller)), dtype=torch.uint8, device=self.device)
             self.sync_problem()
         self.expert_cells[(int(t) + self.t0) % self.H] = int(bool(value))
+        self.revision += 1
 
     def cell_expert(self, t):
         if self.expert_cells is None:
@@ -693,8 +710,8 @@ class BatchedI2c:
                 self.feedforward[:n] = 0  # one fill, no index arithmetic on the device
             else:
                 self.feedforward[self.ring_rows(n)] = 0
-        if self.prior is not self.post:  # keep_prior_joint: the posterior becomes the prior, the old prior buffer is free
-            self._post_spare, self.prior = self.prior, self.post
+        self._fold_posterior()
+        self.revision += 1
 
     def _alpha_from_propagation(self):
         """calculate_alpha(sum of propagated observation covariances) (i2c.py:901-904, 934-939)."""
@@ -833,6 +850,8 @@ class BatchedI2c:
         cov = np.broadcast_to(np.asarray(cov, np.float64), (self.B, self.nx, self.nx))
         self.x0.copy_(torch.as_tensor(np.array(mu.T, order="C"), dtype=self.dtype))
         self.sig_x0.copy_(torch.as_tensor(np.array(pack_sym_np(cov).T, order="C"), dtype=self.dtype))
+        self.revision += 1
+        self.belief_revision += 1
 
     def ckf_filter(self, y, u, sig_zeta, mu=None, cov=None):
         """One cubature Kalman filter step on the belief (mu [nx][B], cov [sym nx][B]; default: the
@@ -843,6 +862,7 @@ class BatchedI2c:
         ny = self.dims.ny
         assert y.shape == (ny, self.B) and u.shape == (self.nu, self.B) and y.dtype == self.dtype
         y, u = y.contiguous(), u.contiguous()  # bound to locals: a temporary copy must outlive the launch
+        self.belief_revision += mu is self.x0 or cov is self.sig_x0
         self._call("i2c_ckf_filter", self._sig_zeta(sig_zeta, True), y, u, mu, cov, self.status)
         return mu, cov
 
@@ -856,6 +876,22 @@ class BatchedI2c:
             self.alpha_init = self.alpha.clone()
             self.alpha_cell = self.alpha.reshape(1, -1).repeat(self.H, 1).contiguous()
             self.refresh_problem()
+            self.revision += 1
+
+    def renew_cell_init(self):
+        """cell_init = deepcopy(cells[0]) (mpc.py:26): the cell shift_horizon() appends is, from now on, today's cell 0."""
+        self.cell_init = self.post[self.t0].clone()
+
+    def set_cell_feedforward(self, t, value):
+        """cells[t].state_action_independence = value (i2c.py:132)."""
+        self.feedforward[(int(t) + self.t0) % self.H] = 1 if value else 0
+        self.revision += 1
+
+    def set_alpha(self, value):
+        """graph.alpha = value: the temperature of every trajectory (a scalar or (B,)), and of every cell in the chain."""
+        self.alpha.copy_(torch.as_tensor(np.broadcast_to(np.asarray(value, float), (self.B,)).copy(), dtype=self.dtype))
+        self._broadcast_alpha()
+        self.revision += 1
 
     def _broadcast_alpha(self):
         """update_xi (i2c.py:976-981): every cell currently in the chain takes the graph's alpha."""
@@ -902,6 +938,7 @@ class BatchedI2c:
         assert self.prior is self.post, "mpc_step() between a sweep and its update_priors()"
         st = _native.I2cMpcStep()
         st.do_filter = int(y is not None)
+        self.belief_revision += y is not None
         if y is not None:
             assert y.shape == (self.dims.ny, self.B) and u.shape == (self.nu, self.B) and y.dtype == self.dtype
             y, u = y.contiguous(), u.contiguous()
@@ -981,6 +1018,7 @@ class BatchedI2c:
         problem, plant = self._plant_problem(plant_params)
         self._call("i2c_plant_step", self._sig_zeta(sig_zeta, eps_y is not None), x, u, eps_x, eps_y, y_out,
                    self.x0 if observe_state else None, z_ref, cost, problem=problem)
+        self.belief_revision += bool(observe_state)
         return y_out
 
     def run_closed_loop(self, n_steps, n_iter, sig_zeta=None, x_true=None, process_noise=True, measurement_noise=True,
@@ -1041,6 +1079,7 @@ class BatchedI2c:
         try:
             self._call("i2c_mpc_episode", C.byref(st), C.byref(ep))
         finally:  # where the call reports the ring, also after an error part-way
+            self.belief_revision += 1
             self.t0, self.terminal_cell = int(ep.t0_out), int(ep.terminal_cell_out)
             self.sync_problem()
         out = {k: v.permute(2, 0, 1) for k, v in hist.items() if v is not None}
@@ -1054,6 +1093,15 @@ class BatchedI2c:
         if self.t0:
             zt = torch.roll(zt, self.t0, 0)  # cell order -> ring rows
         self._install("z", zt.contiguous())
+
+    def set_cell_target(self, t, value):
+        """cells[t].z = value (mpc.py:29-31): the target of ONE cell, (nz, 1) or (B, nz). An engine without per-cell targets gets
+        them here, every other cell with the model's goal."""
+        if self.z is None:
+            self.set_targets(self.zg)
+        v = torch.as_tensor(np.asarray(value, dtype=float).reshape(-1, self.nz).T, dtype=self.dtype, device=self.device)
+        self.z[(int(t) + self.t0) % self.H] = v.expand(self.nz, self.B)
+        self.revision += 1
 
     def rollout(self, n_rollouts=1, policy="linear", process_noise=True, action_noise=False, sample_x0=False,
                 generator=None, want=("xu", "z", "x_final", "z_term"), eps_x0=None, eps_x=None, eps_u=None, model_params=None):
@@ -1187,6 +1235,85 @@ class BatchedI2c:
         log_det_ratio = torch.log(torch.linalg.det(sig2) / torch.linalg.det(sig1))
         trace_ratio = torch.diagonal(torch.linalg.solve(sig2, sig1), dim1=-2, dim2=-1).sum(-1)
         return 0.5 * (log_det_ratio + trace_ratio + dist - nx)
+
+    # ------------------------------------------------------------------ the engine's state: checkpoint and snapshot
+    # THE list of what persists between calls. A new persistent buffer is added here and nowhere else.
+    _STATE_TENSORS = ("post", "alpha", "temp", "feedforward", "status", "x0", "sig_x0", "cell_init")
+    _STATE_OPTIONAL = ("z", "alpha_cell", "alpha_init", "expert_cells")  # None until their setter has allocated them
+    _STATE_LISTS = ("alphas", "alphas_desired", "alphas_pf", "costs_m", "costs_m_var", "costs_pf", "costs_pf_var", "kl_terms")
+    _SNAPSHOT = ("post", "alpha", "alpha_cell", "feedforward", "x0", "sig_x0", "z")  # what restore() puts back (of the two above)
+
+    def state_dict(self):
+        """Everything a resumed EM or MPC run needs, as host tensors and plain scalars: posterior / prior state, temperatures (per
+        trajectory and per cell), the belief x0 / sig_x0, per-cell targets, mode flags, the ring (t0, terminal_cell), tau, and the
+        metric histories. `prior` differs from `post` only when saved between a sweep and its update_priors()."""
+        host = lambda t: t.detach().cpu().clone()  # noqa: E731
+        sd = {k: host(getattr(self, k)) for k in self._STATE_TENSORS}
+        sd["prior"] = host(self.prior)
+        for k in self._STATE_OPTIONAL:
+            v = getattr(self, k)
+            sd[k] = None if v is None else host(v)
+        for k in self._STATE_LISTS:
+            sd[k] = [host(t) for t in getattr(self, k)]
+        sd.update(em_iter=self.em_iter, tau=self.tau, terminal_cell=self.terminal_cell, t0=self.t0, propagate=bool(self._propagate),
+                  use_expert_controller=bool(self.use_expert_controller), horizon=self.H, batch=self.B)
+        return sd
+
+    def load_state_dict(self, sd):
+        """The inverse of state_dict(), on an engine of the same problem. Optional buffers the checkpoint has and this engine has
+        not are allocated through their setters."""
+        if (sd["horizon"], sd["batch"]) != (self.H, self.B):
+            raise ValueError("checkpoint is for another problem (model / horizon / batch)")
+        for k in self._STATE_TENSORS:
+            getattr(self, k).copy_(sd[k])
+        self._fold_posterior()
+        if not torch.equal(sd["prior"], sd["post"]):  # saved between a sweep and its update_priors()
+            self._split_posterior()
+            self.post.copy_(sd["post"])
+            self.prior.copy_(sd["prior"])
+        if sd["alpha_cell"] is not None:
+            self.enable_per_cell_alpha()
+        if sd.get("expert_cells") is not None and self.expert_cells is None:
+            self.set_cell_expert(0, self.use_expert_controller)
+        if sd["z"] is not None and self.z is None:
+            self.set_targets(np.transpose(sd["z"].double().numpy(), (2, 0, 1)))
+        for k in self._STATE_OPTIONAL:
+            if sd.get(k) is not None:
+                getattr(self, k).copy_(sd[k])
+        for k in self._STATE_LISTS:
+            setattr(self, k, [t.to(self.device) for t in sd[k]])
+        self.em_iter, self.tau, self.terminal_cell, self.t0 = int(sd["em_iter"]), int(sd["tau"]), int(sd["terminal_cell"]), int(sd["t0"])
+        self._propagate, self.use_expert_controller = bool(sd["propagate"]), bool(sd["use_expert_controller"])
+        self.refresh_problem()
+        self.revision += 1
+        self.belief_revision += 1
+
+    def snapshot(self):
+        """A device-side copy of the solver state an MPC episode changes (MpcPolicy takes one at construction): the buffers of
+        _SNAPSHOT that exist, in physical row order, and the ring they are valid with."""
+        snap = {k: getattr(self, k).clone() for k in self._SNAPSHOT if getattr(self, k) is not None}
+        snap.update(t0=self.t0, terminal_cell=self.terminal_cell)
+        return snap
+
+    def restore(self, snap):
+        """Back to snapshot(): the buffers it holds, the ring, prior and posterior one buffer again, the status words cleared. NOT
+        restored: `temp`, `cell_init` and the metric histories (an episode does not change the first two and keeps the last)."""
+        self._fold_posterior()
+        for k in self._SNAPSHOT:
+            if k in snap:
+                getattr(self, k).copy_(snap[k])
+        self.status.zero_()
+        self.t0, self.terminal_cell = snap["t0"], snap["terminal_cell"]  # rows were cloned in physical order, at this offset of the ring
+        self.sync_problem()
+        self.revision += 1
+        self.belief_revision += 1
+
+    def clear_history(self, names=("costs_m", "costs_m_var", "costs_pf", "costs_pf_var", "kl_terms")):
+        """Start the named history lists afresh (default: the cost lists and the KL terms, what I2cGraph.reset_metrics clears; the
+        three temperature lists go on)."""
+        for k in names:
+            assert k in self._STATE_LISTS, k
+            setattr(self, k, [])
 
     # ------------------------------------------------------------------ failure reporting
     def failures(self, status=None):

@@ -76,8 +76,7 @@ class I2cCell:
 
     @state_action_independence.setter
     def state_action_independence(self, value):
-        e = self._g.engine
-        e.feedforward[(self.index + e.t0) % e.H] = 1 if value else 0
+        self._g.engine.set_cell_feedforward(self.index, value)
 
     @property
     def use_expert_controller(self):
@@ -210,7 +209,7 @@ class I2cGraph(GraphMetrics):
         self._x0_seen = self._x0_key()
         self.reset_metrics(False)
         self.costs_m_all, self.costs_p_all, self.costs_pf_all = [], [], []
-        self._cache = {}
+        self._cache, self._cache_revision = {}, e.revision
 
     # ------------------------------------------------------------------ plumbing
     def close(self):
@@ -231,16 +230,13 @@ class I2cGraph(GraphMetrics):
         s0 = np.asarray(self.sys.sig_x0, dtype=float)
         key = self._x0_key()
         if key != self._x0_seen:
-            pack_sym_np = core.engine.pack_sym_np
-            e = self.engine
-            e.x0.copy_(torch.as_tensor(x0.reshape(-1, 1), dtype=e.dtype))
-            e.sig_x0.copy_(torch.as_tensor(pack_sym_np(s0).reshape(-1, 1), dtype=e.dtype))
+            self.engine.set_initial_state(x0, s0)
             self._x0_seen = key
 
-    def _invalidate(self):
-        self._cache = {}
-
     def _cached(self, key, fn):
+        """Host copies of the engine's results, kept while the engine's revision is the one they were made at."""
+        if self._cache_revision != self.engine.revision:
+            self._cache, self._cache_revision = {}, self.engine.revision
         if key not in self._cache:
             self._cache[key] = fn()
         return self._cache[key]
@@ -366,13 +362,7 @@ class I2cGraph(GraphMetrics):
 
     def _set_cell_target(self, t, value):
         """Per-cell targets (MPC reference trajectories, mpc.py:29-31)."""
-        e = self.engine
-        if e.z is None:
-            zg = torch.as_tensor(e.zg, dtype=e.dtype, device=e.device)
-            e.z = zg.reshape(1, -1, 1).repeat(self.H, 1, self.B).contiguous()
-            e.refresh_problem()
-        v = torch.as_tensor(np.asarray(value, dtype=float).reshape(-1, e.nz).T, dtype=e.dtype, device=e.device)
-        e.z[(t + e.t0) % e.H] = v.expand(e.nz, self.B)
+        self.engine.set_cell_target(t, value)
 
     # ------------------------------------------------------------------ temperature
     @property
@@ -381,9 +371,7 @@ class I2cGraph(GraphMetrics):
 
     @alpha.setter
     def alpha(self, value):
-        self.engine.alpha.copy_(torch.as_tensor(np.broadcast_to(np.asarray(value, float), (self.B,)).copy(),
-                                                dtype=self.engine.dtype))
-        self.engine._broadcast_alpha()
+        self.engine.set_alpha(value)
 
     @property
     def sig_xi(self):
@@ -449,12 +437,10 @@ class I2cGraph(GraphMetrics):
 
     def _forward_msgs(self):
         self._sync_initial_state()
-        self._invalidate()
         self.engine.forward_sweep()
         self._check()
 
     def _backward_msgs(self):
-        self._invalidate()
         self.engine.backward_sweep()
         self._check()
 
@@ -465,7 +451,6 @@ class I2cGraph(GraphMetrics):
     def _backward_ricatti_msgs(self):
         """i2c.py:888-893 (the reference's spelling). Cells then expose the Riccati-form K / k / sigK and
         nu_x0_b / lambda_x0_b."""
-        self._invalidate()
         self._riccati = self.engine.riccati_sweep()
         self._check()
         self.policy_valid = True
@@ -475,13 +460,11 @@ class I2cGraph(GraphMetrics):
 
     def propagate(self):
         self._sync_initial_state()
-        self._invalidate()
         self.engine.propagate()
         self._check()
 
     def calibrate_alpha(self, only_decrease=False):
         self._sync_initial_state()
-        self._invalidate()
         before = self.alpha
         self.engine.calibrate_alpha(only_decrease)
         logging.info(f"calibrating alpha from propagation {before}->{self.alpha}")
@@ -509,7 +492,6 @@ class I2cGraph(GraphMetrics):
 
     def _maximize(self):
         self.engine.maximize(update_alpha=True)
-        self._invalidate()
         self._checked_iteration()
 
     def compute_update_alpha(self, update_alpha):
@@ -519,7 +501,6 @@ class I2cGraph(GraphMetrics):
 
     def learn_msgs(self):
         self._sync_initial_state()
-        self._invalidate()
         self.engine.learn_msgs()
         self._checked_iteration()
 
@@ -614,12 +595,11 @@ class I2cGraph(GraphMetrics):
 
     # ------------------------------------------------------------------ metrics / persistence
     def reset_metrics(self, extend=True):
-        e = self.engine
         if extend:
             self.costs_m_all.extend(self.costs_m)
             self.costs_pf_all.extend(self.costs_pf)
-        e.costs_m, e.costs_m_var, e.costs_pf, e.costs_pf_var, e.kl_terms = [], [], [], [], []
-        e.em_iter = 0
+        self.engine.clear_history()
+        self.em_iter = 0
         self._pending_metrics = []  # (snapshots of iterations whose entropy entries nobody has read yet, graph_metrics.py)
         for name in ("likelihoods", "likelihoods_xu", "likelihoods_z", "policy_entropy", "sig_eta_entropy",
                      "sig_eta_pf_entropy", "x_prior_entropy", "x_prior_neg_entropy", "propagate_entropy",
@@ -640,53 +620,15 @@ class I2cGraph(GraphMetrics):
         np.save(os.path.join(res_dir, "u_plan.npy"), sq(mu[..., nx:]))
         np.save(os.path.join(res_dir, "z_plan.npy"), sq(mz))
 
-    _STATE_TENSORS = ("post", "alpha", "temp", "feedforward", "status", "x0", "sig_x0", "cell_init")
-    _STATE_OPTIONAL = ("z", "alpha_cell", "alpha_init", "expert_cells")
-    _STATE_LISTS = ("alphas", "alphas_desired", "alphas_pf", "costs_m", "costs_m_var", "costs_pf", "costs_pf_var", "kl_terms")
-
     def state_dict(self):
-        """Everything a resumed EM or MPC run needs (replaces the reference's whole-object dill pickle, i2c.py:1384-1398):
-        posterior / prior state, temperatures (per trajectory and per cell), the belief x0 / sig_x0, per-cell targets,
-        mode flags, the moving terminal-cell index, tau, and the metric histories."""
-        e = self.engine
-        sd = {k: getattr(e, k).detach().cpu().clone() for k in self._STATE_TENSORS}
-        sd["prior"] = e.prior.detach().cpu().clone()
-        for k in self._STATE_OPTIONAL:
-            v = getattr(e, k)
-            sd[k] = None if v is None else v.detach().cpu().clone()
-        for k in self._STATE_LISTS:
-            sd[k] = [t.detach().cpu().clone() for t in getattr(e, k)]
-        sd.update(em_iter=e.em_iter, tau=e.tau, terminal_cell=e.terminal_cell, t0=e.t0, propagate=bool(e._propagate),
-                  use_expert_controller=bool(e.use_expert_controller), horizon=e.H, batch=e.B, model=self.sys.model_name)
-        return sd
+        """Everything a resumed EM or MPC run needs (replaces the reference's whole-object dill pickle, i2c.py:1384-1398): the
+        engine's state (BatchedI2c.state_dict) and the name of the model it belongs to."""
+        return dict(self.engine.state_dict(), model=self.sys.model_name)
 
     def load_state_dict(self, sd):
-        e = self.engine
-        if (sd["horizon"], sd["batch"], sd["model"]) != (e.H, e.B, self.sys.model_name):
+        if sd["model"] != self.sys.model_name:
             raise ValueError("checkpoint is for another problem (model / horizon / batch)")
-        for k in self._STATE_TENSORS:
-            getattr(e, k).copy_(sd[k])
-        if e.prior is not e.post:
-            e._post_spare, e.prior = e.prior, e.post
-        if not torch.equal(sd["prior"], sd["post"]):  # saved between a sweep and its _update_priors()
-            e.post, e._post_spare = e._post_spare, None
-            e.post.copy_(sd["post"])
-            e.prior.copy_(sd["prior"])
-        if sd["alpha_cell"] is not None:
-            e.enable_per_cell_alpha()
-        if sd.get("expert_cells") is not None and e.expert_cells is None:
-            e.set_cell_expert(0, e.use_expert_controller)  # allocates the per-cell flags (and hands them to the library)
-        if sd["z"] is not None and e.z is None:
-            e.set_targets(np.transpose(sd["z"].double().numpy(), (2, 0, 1)))
-        for k in self._STATE_OPTIONAL:
-            if sd.get(k) is not None:
-                getattr(e, k).copy_(sd[k])
-        for k in self._STATE_LISTS:
-            setattr(e, k, [t.to(e.device) for t in sd[k]])
-        e.em_iter, e.tau, e.terminal_cell, e.t0 = int(sd["em_iter"]), int(sd["tau"]), int(sd["terminal_cell"]), int(sd["t0"])
-        e._propagate, e.use_expert_controller = bool(sd["propagate"]), bool(sd["use_expert_controller"])
-        e.refresh_problem()
-        self._invalidate()
+        self.engine.load_state_dict(sd)
 
     def save(self, path, name):
         """i2c.py:1384-1390 (`i2c_{name}.pkl` there, a dill pickle of the whole graph): the solver state as tensors."""
